@@ -10,8 +10,15 @@ event stream to HBM.  Weak scaling: each GPU owns ~1M groups (sharded by
 splitmix64(group id) % N) and the only collective is one RCCL all-reduce of the
 step statistics.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   torchrun --nproc-per-node N bench.py --gpus N ...      (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds everything measured beside the headline figure: the CPU baselines,
+the per-phase HIP events and the separate per-phase pass, the roofline figures
+(with the committed PMC traffic), the decode-only pass of the wire line and the
+host expansion of the e2e line.  --dump-outputs DIR writes what the last timed
+step left for its caller (dump_outputs) as DIR/<name>.npy.
 
 --workload cfg3 / cfg4 runs the other SURVEY.md 8(d) streams (auxiliary lines,
 not the headline metric): cfg3 = 1M x 5 lagging followers (open-loop stream
@@ -275,6 +282,56 @@ def cpu_baseline_wire(n, groups=100_000, W=256, budget_s=10.0, max_steps=20):
                       f"x {n}, {steps} cfg2 steps from wire records, {acks} MsgAppResp in {spent:.2f} s, one core"}
 
 
+DUMP_BLOCK = 1024  # --dump-outputs samples whole blocks of this many group slots ...
+DUMP_BLOCKS = 32   # ... this many of them, drawn with a fixed seed (all groups if there are fewer)
+
+
+def _columns(rec):
+    """A structured array's fields as float64 columns, in declaration order
+    (a per-replica sub-record contributes one column per field and replica)."""
+    cols = []
+    for name in rec.dtype.names:
+        f = rec[name]
+        if f.dtype.names:
+            cols += [f[sub][:, r] for sub in f.dtype.names for r in range(f.shape[1])]
+        else:
+            cols.append(f)
+    return np.stack([np.asarray(c, dtype=np.float64) for c in cols], axis=1)
+
+
+def dump_outputs(dirname, rank, eng, G):
+    """--dump-outputs: what the last timed step left for the caller of hb_step /
+    hb_tick, as float64 .npy files (rank r > 0 writes <name>_rank<r>.npy):
+      stats.npy   the step's HB_STAT_COUNT statistics (abi.STAT_NAMES order);
+      events.npy  the step's events of the sampled groups, [E, 5] = group slot,
+                  type, to, aux, x; grouped by slot, each group's order kept
+                  (the only order the engine promises);
+      groups.npy  the sampled groups' state after the step, [S, 1 + fields] =
+                  slot, then the hb_group fields in declaration order (each
+                  Progress field as HB_MAX_REPLICAS columns).
+    The sample is DUMP_BLOCKS blocks of DUMP_BLOCK consecutive slots drawn with
+    a fixed seed (well under 64 MB at every workload's size); the inputs are
+    seeded, so two builds run with the same arguments are comparable file by file."""
+    os.makedirs(dirname, exist_ok=True)
+    nblk = -(-G // DUMP_BLOCK)
+    pick = np.sort(np.random.default_rng(0x5EEDD0).choice(nblk, min(nblk, DUMP_BLOCKS), replace=False))
+    ids, recs = [], []
+    for b in pick.tolist():
+        first = b * DUMP_BLOCK
+        count = min(DUMP_BLOCK, G - first)
+        ids.append(np.arange(first, first + count, dtype=np.int64))
+        recs.append(eng.get_groups(first, count))
+    ids = np.concatenate(ids)
+    groups = np.concatenate([ids[:, None].astype(np.float64), _columns(np.concatenate(recs))], axis=1)
+    ev = eng.events()
+    ev = ev[np.isin(ev["group"], ids)]
+    ev = ev[np.argsort(ev["group"], kind="stable")]
+    events = np.stack([ev[f].astype(np.float64) for f in ("group", "type", "to", "aux", "x")], axis=1)
+    sfx = f"_rank{rank}" if rank else ""
+    for name, a in (("stats", eng.stats().astype(np.float64)), ("events", events), ("groups", groups)):
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), a)
+
+
 LAYOUT_RO = "role-ordered (led groups in their own partitions; --role-order)"
 
 
@@ -379,6 +436,9 @@ def run_multinode(args):
                 "ready_build", "ready_merge", "advance", "bulk_lookup", "bulk_responses", "bulk_proposals",
                 "batch_reset"])},
            "wall_s": wall}
+    if args.dump_outputs:  # the application's own counters: MsgAppResp stepped, commits advanced
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "counters.npy"), np.array([acks, adv], dtype=np.float64))
     if not args.no_cpu_baseline:
         cb = cpu_baseline(n, groups=min(G, args.cpu_groups), budget_s=min(args.cpu_seconds, 5.0))
         cb["sample"] += " (raft steps only: no Ready assembly, no storage)"
@@ -445,12 +505,19 @@ def main():
                     help="mixed / tick: the groups laid out by role (led groups in partitions of their own), the "
                          "layout a role-ordered slot map in the node would give; a measurement of that map, "
                          "which libhbnode does not build (default: roles interleaved, as a node's ids fall)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what stands beside the headline figure: CPU baselines, per-phase HIP events "
+                         "and the separate per-phase pass, roofline figures, the wire line's decode-only pass, the "
+                         "e2e line's host expansion (default: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (statistics, the events and the "
+                         "state of a fixed seeded sample of groups) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--cpu-groups", type=int, default=200_000)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-threads", type=int, default=min(16, os.cpu_count() or 1),
                     help="shards of the parallel best-case CPU baseline (the GPU box's share is 16 cores)")
-    ap.add_argument("--no-profile", action="store_true", help="skip per-phase HIP events")
+    ap.add_argument("--no-profile", action="store_true", help="--full without the per-phase HIP events")
     ap.add_argument("--e2e-events", choices=["words", "records"], default="words",
                     help="e2e: delta list D2H as compact event words (default) or 16-byte hb_event records")
     ap.add_argument("--overlap", action="store_true",
@@ -465,6 +532,8 @@ def main():
     ap.add_argument("--traffic-json", default=None,
                     help="profiles/<tag>_traffic.json from tools/profile_round.sh (default: newest in profiles/)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_profile = True
     if args.workload == "multinode":
         return run_multinode(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -619,6 +688,8 @@ def run_replication(args, world, rank, local):
     # sanity: every group of every rank commits once per step, nothing faults
     ok = commits == G_total * args.steps and int(st[abi.HB_STAT_FAULTS]) == 0 and \
         appresp == G_total * (n - 1) * args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, eng, G)
     route_t = torch.tensor([route["seconds"]], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(route_t, op=dist.ReduceOp.MAX)
@@ -840,8 +911,10 @@ def run_e2e(args, world, rank, local, dev, torch, dist):
         sec_t = sec_t.to(dev)
         dist.all_reduce(sec_t, op=dist.ReduceOp.MAX)
     sec = float(sec_t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, eng, G)
     expand = {}
-    if words_mode:  # the last step's words expanded on the host, untimed above
+    if words_mode and args.full:  # the last step's words expanded on the host, untimed above
         lb = (total - 1) % 2
         w = h_w[lb].numpy()[: int(h_tot[lb][0])].view(np.uint64)
         c = h_cnt[lb].numpy().view(np.uint32)
@@ -873,7 +946,9 @@ def run_e2e(args, world, rank, local, dev, torch, dist):
                                  "events_d2h": 1e3 * t_ev / steps},
            "bytes_per_step": {"h2d_batch": h2d, "d2h_delta": d2h},
            "pcie_gbs": round((h2d + d2h) / (sec / steps) / 1e9, 2),
-           "events_per_step": nev_total // steps, "words_per_step": nword_total // steps if words_mode else None,
+           # (words mode counts records by expanding the words on the host: --full)
+           "events_per_step": nev_total // steps if args.full or not words_mode else None,
+           "words_per_step": nword_total // steps if words_mode else None,
            **expand, "parity_sanity": bool(ok),
            "timing": "wall clock: hb_step (H2D inside) + " + how,
            "cpu_baseline": None}
@@ -973,13 +1048,12 @@ def run_aux(args, world, rank, local, dev, torch, dist):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream)
         for k in range(args.warmup, total):
-            one(k, "apply" if (k - args.warmup) % 4 == 0 else False)  # HIP events around k_apply_fast
+            one(k, "apply" if args.full and (k - args.warmup) % 4 == 0 else False)  # HIP events around k_apply_fast
         e1.record(stream)
         torch.cuda.synchronize()
         ms_local = e0.elapsed_time(e1)
         st_acc = stats.cpu().numpy().astype(np.uint64)
-        ph, nph = eng.phase_ms()
-        apply_us = float(ph[abi.HB_PHASE_APPLY]) * 1e3
+        apply_us = float(eng.phase_ms()[0][abi.HB_PHASE_APPLY]) * 1e3 if args.full else 0.0
         fused_x = bool(eng.step_kernels() & abi.HB_KERN_ROUTE_FAST)  # (the apply phase brackets k_route_fast)
         timing = "K steps back to back, inputs resident in HBM"
     elif args.workload == "tick":
@@ -1060,15 +1134,17 @@ def run_aux(args, world, rank, local, dev, torch, dist):
         ms_local = e0.elapsed_time(e1)
         st_acc = stats.cpu().numpy().astype(np.uint64)
         bad = int((status != abi.HB_WIRE_OK).sum().item())
-        # the decode kernel alone (it only writes the batch arrays, so it replays)
+        # --full: the decode kernel alone (it only writes the batch arrays, so it replays)
         eng.set_stats_accum(None)
-        d0, d1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        d0.record(stream)
-        for k in range(args.warmup, total):
-            eng.decode(recs[k][0], recs[k][1], recs[k][2], d_group, out, status)
-        d1.record(stream)
-        torch.cuda.synchronize()
-        dec_us = d0.elapsed_time(d1) * 1e3 / args.steps
+        dec_us = None
+        if args.full:
+            d0, d1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            d0.record(stream)
+            for k in range(args.warmup, total):
+                eng.decode(recs[k][0], recs[k][1], recs[k][2], d_group, out, status)
+            d1.record(stream)
+            torch.cuda.synchronize()
+            dec_us = d0.elapsed_time(d1) * 1e3 / args.steps
         # + the From -> slot lookup: the group's n peer ids and n (one 64-byte row)
         alg = wire_bytes + nmsg * (8 + 4 + 4) + nmsg * (n + 1) * 8 + nmsg * (4 + 4 + 8 + 8 + 8 + 1)
         timing = "K (hb_decode + hb_step) back to back, wire records resident in HBM"
@@ -1114,6 +1190,8 @@ def run_aux(args, world, rank, local, dev, torch, dist):
         timing = ("per-step HIP event times, each step's launches queued behind a device-side wait (even timed "
                   "steps; the odd ones are timed from an idle GPU, launch latency included: ms_per_step_idle_gpu); "
                   "stream generation from the engine state between steps excluded")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, eng, G)
     ms_t = torch.tensor([ms_local], dtype=torch.float64, device=dev)
     st_t = torch.from_numpy(st_acc.view(np.int64).copy()).to(dev)
     if world > 1:
@@ -1125,16 +1203,17 @@ def run_aux(args, world, rank, local, dev, torch, dist):
     if args.workload == "wire":
         metric, unit, val = "MsgAppResp applied/sec from raftpb wire records (hb_decode + hb_step, cfg2)", \
             "MsgAppResp/s", int(st[abi.HB_STAT_APPRESP]) / sec
-        extra = {"commits_per_s": int(st[abi.HB_STAT_COMMITS]) / sec,
-                 "decode": {"us_per_batch": round(dec_us, 2), "records_per_s": nmsg / (dec_us * 1e-6),
-                            "wire_bytes_per_batch": wire_bytes, "records_not_ok": bad,
-                            "roofline": {"bound": "hbm", "kernel": "k_decode",
-                                         "achieved": round(alg / (dec_us * 1e-6) / 1e9, 1), "peak": HBM_PEAK_GBS,
-                                         "unit": "GB/s", "frac": round(alg / (dec_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
-                                         "alg_bytes_per_launch": alg,
-                                         "alg_bytes_note": f"record bytes + off/len/group 16 B + peer ids and "
-                                                           f"n {(n + 1) * 8} B + batch record 32 B + status 1 B "
-                                                           f"per record"}}}
+        dec = {"wire_bytes_per_batch": wire_bytes, "records_not_ok": bad}
+        if dec_us is not None:
+            dec = {"us_per_batch": round(dec_us, 2), "records_per_s": nmsg / (dec_us * 1e-6), **dec,
+                   "roofline": {"bound": "hbm", "kernel": "k_decode",
+                                "achieved": round(alg / (dec_us * 1e-6) / 1e9, 1), "peak": HBM_PEAK_GBS,
+                                "unit": "GB/s", "frac": round(alg / (dec_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
+                                "alg_bytes_per_launch": alg,
+                                "alg_bytes_note": f"record bytes + off/len/group 16 B + peer ids and "
+                                                  f"n {(n + 1) * 8} B + batch record 32 B + status 1 B "
+                                                  f"per record"}}
+        extra = {"commits_per_s": int(st[abi.HB_STAT_COMMITS]) / sec, "decode": dec}
         ok = int(st[abi.HB_STAT_COMMITS]) == world * G * args.steps and bad == 0 and int(st[abi.HB_STAT_FAULTS]) == 0
         wl = f"wire: cfg2 ({G} raft groups x {n} per GPU), MsgAppResp as raftpb wire records"
         data = "synthetic (cfg2 stream encoded with the reference's MarshalTo layout)"
@@ -1185,7 +1264,7 @@ def run_aux(args, world, rank, local, dev, torch, dist):
             knames = [f"k_apply_lead<{n}, true>", f"k_apply_lead<{n}>"]
         ach_k = launch_alg / (apply_us * 1e-6) / 1e9 if apply_us > 0 else 0.0
         tr, tsrc = pmc_traffic(args.traffic_json, knames, G, n, apply_us, workload=args.workload, layout=LAYOUT_RO
-                               if args.role_order else None)
+                               if args.role_order else None) if args.full else (None, None)
         extra = {"commits_per_s": int(st[abi.HB_STAT_COMMITS]) / sec, "entries_per_s": int(st[abi.HB_STAT_ENTRIES]) / sec,
                  "roofline": {"bound": "hbm", "kernel": kname, "achieved": round(ach_k, 1), "peak": HBM_PEAK_GBS,
                               "unit": "GB/s", "frac": round(ach_k / HBM_PEAK_GBS, 4), "traffic": tr,
@@ -1195,6 +1274,8 @@ def run_aux(args, world, rank, local, dev, torch, dist):
                                   f"; a led group {alg_bytes_per_group(n)} B (the cfg2 step: proposal + {n - 1} "
                                   f"MsgAppResp, SURVEY.md 8(d))" if n_led else ""),
                               "step_frac": round(alg / args.steps / (ms / args.steps * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}}
+        if not args.full:  # (no HIP events around the kernel in a plain run)
+            del extra["roofline"]
         msgs_per_step = 2 * n_fol + (n - 1) * n_led
         ok = int(st[abi.HB_STAT_COMMITS]) == world * G * args.steps and \
             int(st[abi.HB_STAT_MSGS]) == world * msgs_per_step * args.steps and int(st[abi.HB_STAT_FAULTS]) == 0
@@ -1240,7 +1321,7 @@ def run_aux(args, world, rank, local, dev, torch, dist):
         ok = int(st[abi.HB_STAT_FAULTS]) == 0
         wl = f"cfg3: {G} raft groups x {n} per GPU, lagging followers (W={W})"
         data = "synthetic (seeded open-loop cfg3 stream generated from the engine state each step)"
-    if args.workload in ("cfg3", "cfg4", "tick"):
+    if args.full and args.workload in ("cfg3", "cfg4", "tick"):
         # whole-step roofline (several kernels share the step; per-kernel times: profiles/*kernel_stats.csv)
         ach = alg / (ms / args.steps * 1e-3) / args.steps / 1e9 if ms > 0 else 0.0
         tr, tsrc = step_traffic(args.traffic_json, args.workload, G, n, ms / args.steps,

@@ -13,7 +13,7 @@ for SPEC in $WLS; do
     lib=$PWD/etcd_amd/libhipbatch_$v.so; [ "$v" = full ] && lib=$PWD/etcd_amd/libhipbatch.so
     EV=""; XA=""
     case $v in env:*) lib=$PWD/etcd_amd/libhipbatch.so; EV=${v#env:};; arg:*) lib=$PWD/etcd_amd/libhipbatch.so; XA=${v#arg:};; esac
-    env HB_LIB=$lib $EV timeout -k 10 300 python3 bench.py --workload $WL $RA --steps 20 --warmup 5 --no-cpu-baseline $XA \
+    env HB_LIB=$lib $EV timeout -k 10 300 python3 bench.py --workload $WL $RA --full --steps 20 --warmup 5 --no-cpu-baseline $XA \
       > "gpurun_out/ab/$WL${RA:+_r}.${v//[:=\/ ]/_}.json"
     F="gpurun_out/ab/$WL${RA:+_r}.${v//[:=\/ ]/_}.json" WL=$SPEC V=$v python3 - <<'PY'
 import json, os

@@ -10,7 +10,7 @@ cd "$ROOT"
 if [ -n "${2:-}" ] && [ "$2" != full ]; then export HB_LIB=$ROOT/etcd_amd/libhipbatch_$2.so; fi
 for w in ${3:-cfg4 cfg3}; do
   timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$w" -o run -- \
-      python3 bench.py --workload $w --steps 4 --warmup 1 --no-cpu-baseline > "$OUT/$w.json" 2> "$OUT/$w.err"
+      python3 bench.py --workload $w --full --steps 4 --warmup 1 --no-cpu-baseline > "$OUT/$w.json" 2> "$OUT/$w.err"
   echo "== $w"; python3 - "$OUT/$w" <<'PY'
 import csv, glob, sys
 st = glob.glob(f"{sys.argv[1]}/**/*kernel_stats.csv", recursive=True)
