@@ -21,6 +21,7 @@
 // device batch, and the host only replays the events the device returns.
 #include "../../include/hbnode.h"
 #include "hbpool.h"
+#include "hbslots.h"
 
 #include <algorithm>
 #include <atomic>
@@ -758,7 +759,9 @@ inline void bump(uint64_t& x, bool shared) {
 // of its own: the workers push to them on every group)
 struct alignas(64) Lists {
   std::vector<Group*> touched, content, delivered, reload, stepped, bx;
+  std::vector<uint32_t> roled;  // HBN_PLACE_ROLE: slots whose group became or stopped being led (read by repack)
   void clear() {
+    roled.clear();
     touched.clear();
     content.clear();
     delivered.clear();
@@ -891,7 +894,14 @@ struct hbn_node {
   uint64_t max_msg = HB_NO_LIMIT, max_batch = 0;
   IdMap groups;
   std::vector<Group*> by_slot;
-  std::vector<uint32_t> free_slots;
+  std::vector<uint32_t> free_slots;  // HBN_PLACE_ARRIVAL: the free list; under HBN_PLACE_ROLE smap owns the slots
+  // slot placement (hbn_set_placement): the role-ordered map and its re-pack scratch
+  uint32_t place = HBN_PLACE_ARRIVAL;
+  hbslots::SlotMap smap;
+  std::vector<hbslots::Move> mv;
+  std::vector<uint32_t> mv_src, mv_dst;
+  std::vector<Group*> mv_g;
+  uint64_t moves_total = 0, repacks = 0;
   // pending device batch (host SoA, HB_STEP_HOST_PTRS; the bulk paths size the
   // arrays and their workers write every element, so growth does not zero them)
   RawVec<uint32_t> b_group, b_info;
@@ -1009,11 +1019,24 @@ void note_solo(hbn_node* n, Group& g) {
   }
 }
 
+// A slot for a group that is not led.  HBN_PLACE_ROLE: the slot above the
+// other range (hbslots.h); a group that is led all the same tells the map.
 uint32_t alloc_slot(hbn_node* n) {
+  if (n->place == HBN_PLACE_ROLE) {
+    const uint32_t s = n->smap.alloc();
+    if (s == hbslots::NONE) throw Fail{HB_ENOMEM};
+    return s;
+  }
   if (n->free_slots.empty()) throw Fail{HB_ENOMEM};
   const uint32_t s = n->free_slots.back();
   n->free_slots.pop_back();
   return s;
+}
+// the group of `slot` left the device (hb_remove_groups done)
+void free_slot(hbn_node* n, uint32_t slot) {
+  n->by_slot[slot] = nullptr;
+  if (n->place == HBN_PLACE_ROLE) n->smap.release(slot);
+  else n->free_slots.push_back(slot);
 }
 
 // ---------------------------------------------------------------- event replay
@@ -1122,6 +1145,8 @@ void on_event(hbn_node* n, Group& g, const hb_event& e, Lists& L) {
     case HB_EV_STATE: {
       const uint32_t st = (uint32_t)(e.x & 0xFF), lref = (uint32_t)((e.x >> 8) & 0xFF),
                      vref = (uint32_t)((e.x >> 16) & 0xFF);
+      if (n->place == HBN_PLACE_ROLE && (g.state == HB_STATE_LEADER) != (st == HB_STATE_LEADER))
+        L.roled.push_back(g.slot);  // fixed at the next re-pack
       g.state = st;
       g.lead = (e.aux & HB_STATE_OTH_LEAD) ? g.cur_from : id_of_ref(g, n->id, lref, g.lead);
       g.vote = (e.aux & HB_STATE_OTH_VOTE) ? g.cur_from : id_of_ref(g, n->id, vref, g.vote);
@@ -1617,6 +1642,38 @@ void flush(hbn_node* n) {
     g->reload_nodes.clear();
   }
   n->reload.clear();
+}
+
+// HBN_PLACE_ROLE: restore the role-ordered layout (hbslots.h) with one
+// hb_move_groups call.  Runs on the API thread once the pending batch and the
+// queued loads are on the device, so no batch row and no pending record names a
+// slot; everything else reaches a group's slot through Group::slot / by_slot.
+void repack(hbn_node* n) {
+  if (!n->b_group.empty() || !n->pend_rec.empty() || !n->pend_tm.empty()) flush(n);
+  for (Lists& l : n->lists) {  // role changes the replay saw (a stale slot just reports its present group)
+    for (uint32_t s : l.roled)
+      if (s < n->by_slot.size() && n->by_slot[s]) n->smap.set_led(s, n->by_slot[s]->state == HB_STATE_LEADER);
+    l.roled.clear();
+  }
+  n->smap.plan(n->mv);
+  ++n->repacks;
+  const size_t k = n->mv.size();
+  if (k == 0) return;
+  n->mv_src.resize(k);
+  n->mv_dst.resize(k);
+  n->mv_g.resize(k);
+  for (size_t i = 0; i < k; ++i) {
+    n->mv_src[i] = n->mv[i].src;
+    n->mv_dst[i] = n->mv[i].dst;
+    n->mv_g[i] = n->by_slot[n->mv[i].src];
+  }
+  check(hb_move_groups(n->h, (uint32_t)k, n->mv_src.data(), n->mv_dst.data()));
+  for (size_t i = 0; i < k; ++i) n->by_slot[n->mv_src[i]] = nullptr;
+  for (size_t i = 0; i < k; ++i) {
+    n->by_slot[n->mv_dst[i]] = n->mv_g[i];
+    n->mv_g[i]->slot = n->mv_dst[i];
+  }
+  n->moves_total += k;
 }
 
 bool is_response(uint32_t t) {  // IsResponseMsg raft/util.go:53-55
@@ -2131,8 +2188,7 @@ void reload_prs(hbn_node* n, Group& g, const std::vector<uint64_t>& new_peers,
   if (new_peers.empty()) {
     if (g.slot != NO_SLOT) {
       check(hb_remove_groups(n->h, g.slot, 1));
-      n->by_slot[g.slot] = nullptr;
-      n->free_slots.push_back(g.slot);
+      free_slot(n, g.slot);
       g.slot = NO_SLOT;
     }
     return;
@@ -2178,6 +2234,7 @@ void reload_prs(hbn_node* n, Group& g, const std::vector<uint64_t>& new_peers,
   } else {
     g.slot = alloc_slot(n);
     n->by_slot[g.slot] = &g;
+    if (n->place == HBN_PLACE_ROLE) n->smap.set_led(g.slot, g.state == HB_STATE_LEADER);
     tm.elapsed = 0;
     tm.rand_pos = 0;
   }
@@ -2602,8 +2659,7 @@ int hbn_remove_group(hbn_node* n, uint64_t group) {
     Group& g = *gp;
     if (g.slot != NO_SLOT) {
       check(hb_remove_groups(n->h, g.slot, 1));
-      n->by_slot[g.slot] = nullptr;
-      n->free_slots.push_back(g.slot);
+      free_slot(n, g.slot);
     }
     if (g.log.st) drop_user(g.log.st, n, group);
     for (auto* v : {&n->touched, &n->content, &n->delivered, &n->stepped, &n->bounds, &n->pend_sz, &n->pend_tr,
@@ -2732,6 +2788,11 @@ int hbn_set_threads(hbn_node* n, uint32_t threads) {
   if (!n || threads == 0 || threads > 256) return HB_EINVAL;
   return guarded([&] {
     n->pool.reset(new Pool(threads));
+    for (size_t t = 1; t < n->lists.size(); ++t) {  // (role changes awaiting the next re-pack survive a shrink)
+      std::vector<uint32_t>& r = n->lists[t].roled;
+      n->lists[0].roled.insert(n->lists[0].roled.end(), r.begin(), r.end());
+      r.clear();
+    }
     n->lists.resize(threads);
     if (n->arenas.size() < threads) n->arenas.resize(threads);  // (the last Ready stays valid)
   });
@@ -2911,6 +2972,48 @@ int hbn_advance(hbn_node* n, const uint64_t* groups, uint64_t count) {
     merge(n->content, n->lists, &Lists::content);
     merge(n->touched, n->lists, &Lists::touched);
     n->awaiting_advance = false;
+    if (n->place == HBN_PLACE_ROLE) repack(n);
+  });
+}
+
+int hbn_set_placement(hbn_node* n, uint32_t mode) {
+  if (!n || (mode != HBN_PLACE_ARRIVAL && mode != HBN_PLACE_ROLE)) return HB_EINVAL;
+  return guarded([&] {
+    flush(n);
+    if (mode == n->place) return;
+    for (Lists& l : n->lists) l.roled.clear();
+    if (mode == HBN_PLACE_ROLE) {  // adopt the arrival-order map as it stands, then the first re-pack
+      std::vector<uint8_t> roles(n->capacity, hbslots::EMPTY);
+      for (uint32_t s = 0; s < n->capacity; ++s)
+        if (const Group* g = n->by_slot[s]) roles[s] = g->state == HB_STATE_LEADER ? hbslots::LED : hbslots::OTHER;
+      n->smap.adopt(roles);
+      n->free_slots.clear();
+      n->place = HBN_PLACE_ROLE;
+      repack(n);
+    } else {  // back to the free list; every group stays where it is
+      n->place = HBN_PLACE_ARRIVAL;
+      n->free_slots.clear();
+      for (uint32_t s = n->capacity; s > 0; --s)
+        if (!n->by_slot[s - 1]) n->free_slots.push_back(s - 1);
+    }
+  });
+}
+
+int hbn_placement_stats(hbn_node* n, hbn_placement* out) {
+  if (!n || !out) return HB_EINVAL;
+  return guarded([&] {
+    std::memset(out, 0, sizeof(*out));
+    out->mode = n->place;
+    out->moves_total = n->moves_total;
+    out->repacks = n->repacks;
+    for (uint32_t t = 0; t < n->capacity; t += hbslots::TILE) {
+      uint32_t led = 0, oth = 0;
+      for (uint32_t s = t; s < n->capacity && s < t + hbslots::TILE; ++s)
+        if (const Group* g = n->by_slot[s]) (g->state == HB_STATE_LEADER ? led : oth)++;
+      out->led += led;
+      out->other += oth;
+      out->mixed_tiles += led && oth;
+    }
   });
 }
 

@@ -3293,6 +3293,160 @@ __global__ void k_get_ins(DevState S, uint32_t g, uint32_t s, uint64_t* vals, ui
   }
 }
 
+// ============================================================================
+// hb_move_groups: slot dst[i] takes every device word of slot src[i].  All
+// sources are read (k_move_gather, k_move_ring<false>) into a staging buffer
+// before any destination is written (k_move_scatter, k_move_ring<true>), so
+// swaps, cycles and chains need no ordering.  The raw words travel: the lazy
+// forms of meta (M_RS / M_SM / M_TL / M_NC) stay exactly as they are.
+// ============================================================================
+struct MoveArgs {
+  uint32_t count, nvac;
+  const uint32_t* src;      // [count]
+  const uint32_t* dst;      // [count]
+  const uint32_t* vac;      // [nvac] slots in src but not in dst: they end up empty ...
+  const uint64_t* vac_szx;  // [nvac] ... and own the extents the overwritten slots held
+  const uint64_t* vac_trx;  // [nvac]
+  uint64_t* stage;          // [move_words()][count], word-major (a lane per move: coalesced)
+  uint64_t* peer;           // the peer-id table or null
+  uint64_t* jobs;           // [count x nmax] non-empty inflight windows: (move * 8 + slot) | ring-stage offset << 28
+  unsigned long long* ctr;  // [0] jobs, [1] ring-stage words
+  uint64_t* rstage;         // the windows' words, window after window
+};
+constexpr uint32_t MV_PM_WORD = 8 + 3;  // stage word of slot s's pm: MV_PM_WORD + 4 s
+constexpr uint32_t MV_JOB_SHIFT = 28;   // a job's low bits: move (< 2^24 groups) * 8 + slot
+__host__ __device__ inline uint32_t move_words(uint32_t nmax, bool sized, bool peers) {
+  return 8 + 4 * nmax + 2 + 2 + (sized ? 2u : 0u) + (peers ? HB_PEER_ROW : 0u);
+}
+// the live window of a staged pm word (start, count), as k_get_ins reads it
+__device__ __forceinline__ void move_window(const DevState& S, uint64_t meta, uint32_t pm, uint32_t* start,
+                                            uint32_t* count) {
+  const uint32_t c = (meta & M_RS) ? 0u : pm_count(pm);  // the reset form: an empty window
+  *count = c < S.W ? c : S.W;
+  *start = pm_start(pm) % S.W;
+}
+
+__global__ void __launch_bounds__(256) k_move_gather(DevState S, MoveArgs a) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.count) return;
+  const uint32_t g = a.src[i];
+  uint64_t* w = a.stage + i;
+  auto put = [&](uint64_t x) {
+    *w = x;
+    w += a.count;
+  };
+  const uint64_t m = S.meta[g];
+  put(S.term[g]);
+  put(S.commit[g]);
+  put(S.first[g]);
+  put(S.last[g]);
+  put(S.tfirst[g]);
+  put(S.tlast[g]);
+  put(S.snap[g]);
+  put(m);
+  for (uint32_t s = 0; s < S.nmax; ++s) {
+    const size_t o = (size_t)s * S.G + g;
+    const uint32_t p = S.pm[o];
+    put(S.match[o]);
+    put(S.next[o]);
+    put(S.pending[o]);
+    put(p);
+    uint32_t start, cnt;
+    move_window(S, m, p, &start, &cnt);
+    if (cnt && g != a.dst[i]) {  // a window to carry: its place in the ring stage, and a wave's job
+      const uint64_t off = atomicAdd(a.ctr + 1, (unsigned long long)cnt);
+      const uint64_t j = atomicAdd(a.ctr, 1ull);
+      a.jobs[j] = (uint64_t)(i * 8u + s) | (off << MV_JOB_SHIFT);
+    }
+  }
+  put((uint64_t)S.elapsed[g] | ((uint64_t)S.rpos[g] << 32));
+  put(S.tcfg[g]);
+  put(S.trc[g]);
+  put(S.trx[g]);
+  if (S.szx) {
+    put(S.szlo[g]);
+    put(S.szx[g]);
+  }
+  if (a.peer)
+    for (uint32_t k = 0; k < HB_PEER_ROW; ++k) put(a.peer[(size_t)g * HB_PEER_ROW + k]);
+}
+
+// lanes [0, count): move i's words into dst[i]; lanes [count, count + nvac): a vacated slot
+__global__ void __launch_bounds__(256) k_move_scatter(DevState S, MoveArgs a) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.count) {
+    const uint32_t v = i - a.count;
+    if (v >= a.nvac) return;
+    const uint32_t g = a.vac[v];
+    S.meta[g] = 0;  // as hb_remove_groups leaves it; the rings start over in their new extents
+    S.trc[g] = 0;
+    S.trx[g] = a.vac_trx[v];
+    if (S.szx) {
+      S.szlo[g] = S.last[g];
+      S.szx[g] = a.vac_szx[v];
+    }
+    return;
+  }
+  const uint32_t g = a.dst[i];
+  const uint64_t* w = a.stage + i;
+  auto get = [&]() {
+    const uint64_t x = *w;
+    w += a.count;
+    return x;
+  };
+  S.term[g] = get();
+  S.commit[g] = get();
+  S.first[g] = get();
+  S.last[g] = get();
+  S.tfirst[g] = get();
+  S.tlast[g] = get();
+  S.snap[g] = get();
+  S.meta[g] = get();
+  for (uint32_t s = 0; s < S.nmax; ++s) {
+    const size_t o = (size_t)s * S.G + g;
+    S.match[o] = get();
+    S.next[o] = get();
+    S.pending[o] = get();
+    S.pm[o] = (uint32_t)get();
+  }
+  const uint64_t t = get();
+  S.elapsed[g] = (uint32_t)t;
+  S.rpos[g] = (uint32_t)(t >> 32);
+  S.tcfg[g] = (uint32_t)get();
+  S.trc[g] = get();
+  S.trx[g] = get();
+  if (S.szx) {
+    S.szlo[g] = get();
+    S.szx[g] = get();
+  }
+  if (a.peer)
+    for (uint32_t k = 0; k < HB_PEER_ROW; ++k) a.peer[(size_t)g * HB_PEER_ROW + k] = get();
+}
+
+// A wave per job (move, follower slot): the live window's words between the
+// inflight ring and the ring stage, at the same ring positions (OUT: stage -> dst).
+template <bool OUT>
+__global__ void __launch_bounds__(256) k_move_ring(DevState S, MoveArgs a, uint32_t njobs) {
+  const uint32_t j = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64, lane = threadIdx.x & 63u;
+  if (j >= njobs) return;
+  const uint64_t job = a.jobs[j];
+  const uint32_t is = (uint32_t)(job & ((1ull << MV_JOB_SHIFT) - 1)), i = is >> 3, s = is & 7u;
+  const uint64_t off = job >> MV_JOB_SHIFT;
+  if (i >= a.count || s >= S.nmax) return;
+  const uint32_t g = OUT ? a.dst[i] : a.src[i];
+  const uint64_t m = a.stage[(size_t)7 * a.count + i];
+  const uint32_t p = (uint32_t)a.stage[(size_t)(MV_PM_WORD + 4 * s) * a.count + i];
+  uint32_t start, cnt;
+  move_window(S, m, p, &start, &cnt);
+  for (uint32_t k = lane; k < cnt; k += 64) {
+    uint32_t idx = start + k;
+    if (idx >= S.W) idx -= S.W;
+    uint64_t* r = S.ring + ((size_t)s * S.W + idx) * S.G + g;
+    if (OUT) *r = a.rstage[off + k];
+    else a.rstage[off + k] = *r;
+  }
+}
+
 // Dense gather of the chunked events: chunk c (counts[c] compact words at
 // base + offs[c]; chunk 2p / 2p+1 = partition p's P / M chunk) is expanded
 // into public hb_event records at out + dst[c], dst = exclusive scan of the
@@ -3580,6 +3734,18 @@ struct hb_handle {
   uint64_t evw_cap = 0;
   uint64_t* rnd = nullptr;        // the r.rand stream (hb_set_rand), grown on demand
   uint64_t rnd_cap = 0;
+  // hb_move_groups scratch, grown on demand and reused (capacities in u64 words)
+  uint64_t* mv_in = nullptr;      // the call's slot lists and vacated slots' extents (one H2D copy)
+  uint64_t mv_in_cap = 0;
+  uint64_t* mv_stage = nullptr;   // [move_words][count]
+  uint64_t mv_stage_cap = 0;
+  uint64_t* mv_jobs = nullptr;    // [count x nmax]
+  uint64_t mv_jobs_cap = 0;
+  uint64_t* mv_rstage = nullptr;  // the carried inflight windows
+  uint64_t mv_rstage_cap = 0;
+  unsigned long long* mv_ctr = nullptr;  // [2] jobs, ring-stage words
+  std::vector<uint64_t> mv_host;  // host image of mv_in
+  std::vector<uint8_t> mv_mark;   // [G] validation marks: 1 in src, 2 in dst (all zero between calls)
   static constexpr uint32_t PROF_RING = 256;
   // per profiled step: prep start, prep end (prep stream), apply start, fast end,
   // general end, finish end (apply stream)
@@ -3992,6 +4158,8 @@ int hb_destroy(hb_handle* h) {
     if (ps.applied) (void)hipEventDestroy(ps.applied);
   }
   if (h->rnd) (void)hipFree(h->rnd);
+  for (void* p : {(void*)h->mv_in, (void*)h->mv_stage, (void*)h->mv_jobs, (void*)h->mv_rstage, (void*)h->mv_ctr})
+    if (p) (void)hipFree(p);
   if (h->evx) (void)hipFree(h->evx);
   if (h->evw) (void)hipFree(h->evw);
   for (PrepSet& ps : h->set)
@@ -4080,6 +4248,116 @@ int hb_remove_groups(hb_handle* h, uint32_t first, uint32_t count) {
   DeviceGuard guard(h->device);
   hipLaunchKernelGGL(k_remove, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->st, first, count);
   HB_CHECK(hipStreamSynchronize(h->stream));
+  return HB_OK;
+}
+
+// a scratch buffer of at least `need` u64 words (the old one is idle: every call that uses it synchronizes)
+static int mv_grow(void** p, uint64_t* cap, uint64_t need) {
+  if (need <= *cap) return HB_OK;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  const uint64_t want = std::max<uint64_t>(need, 2 * *cap);
+  *cap = 0;
+  if (hipMalloc(p, want * 8) != hipSuccess) return HB_ENOMEM;
+  *cap = want;
+  return HB_OK;
+}
+
+int hb_move_groups(hb_handle* h, uint32_t count, const uint32_t* src, const uint32_t* dst) {
+  if (!h || (count && (!src || !dst))) return HB_EINVAL;
+  if (count == 0) return HB_OK;
+  if (count > h->G) return HB_EINVAL;  // more pairs than slots: a duplicate
+  // validation: every slot in range, src distinct, dst distinct (marks: 1 in src, 2 in dst)
+  if (h->mv_mark.size() != h->G) h->mv_mark.assign(h->G, 0);
+  std::vector<uint8_t>& mark = h->mv_mark;
+  uint32_t seen = 0;
+  bool ok = true;
+  for (; seen < count; ++seen) {
+    const uint32_t s = src[seen], d = dst[seen];
+    if (s >= h->G || d >= h->G || (mark[s] & 1) || (mark[d] & 2)) {
+      ok = false;
+      break;
+    }
+    mark[s] |= 1;
+    mark[d] |= 2;
+  }
+  // vacated slots (in src, not in dst) take over the log extents of the
+  // overwritten ones (in dst, not in src): equally many, every slot keeps one of each kind
+  std::vector<uint32_t> vac, over;
+  if (ok)
+    for (uint32_t i = 0; i < count; ++i) {
+      if (!(mark[src[i]] & 2)) vac.push_back(src[i]);
+      if (!(mark[dst[i]] & 1)) over.push_back(dst[i]);
+    }
+  for (uint32_t i = 0; i < seen; ++i) mark[src[i]] = mark[dst[i]] = 0;
+  if (!ok || vac.size() != over.size()) return HB_EINVAL;
+  const uint32_t nvac = (uint32_t)vac.size();
+  const bool sized = h->st.szx != nullptr;
+
+  DeviceGuard guard(h->device);
+  const uint32_t NW = move_words(h->nmax, sized, h->peer != nullptr);
+  const uint64_t in_words = 2ull * nvac + (2ull * count + nvac + 1) / 2;
+  int rc = mv_grow(reinterpret_cast<void**>(&h->mv_in), &h->mv_in_cap, in_words);
+  if (rc == HB_OK) rc = mv_grow(reinterpret_cast<void**>(&h->mv_stage), &h->mv_stage_cap, (uint64_t)NW * count);
+  if (rc == HB_OK) rc = mv_grow(reinterpret_cast<void**>(&h->mv_jobs), &h->mv_jobs_cap, (uint64_t)h->nmax * count);
+  if (rc != HB_OK) return rc;
+  if (!h->mv_ctr) HB_CHECK(hipMalloc(&h->mv_ctr, 16));
+  // one upload: the vacated slots' new extent words (u64), then src, dst, vac (u32)
+  h->mv_host.assign(in_words, 0);
+  uint32_t* hsrc = reinterpret_cast<uint32_t*>(h->mv_host.data() + 2ull * nvac);
+  for (uint32_t v = 0; v < nvac; ++v) {
+    h->mv_host[v] = sized ? h->h_szx[over[v]] : 0;
+    h->mv_host[nvac + v] = h->h_trx[over[v]];
+  }
+  std::memcpy(hsrc, src, 4ull * count);
+  std::memcpy(hsrc + count, dst, 4ull * count);
+  if (nvac) std::memcpy(hsrc + 2ull * count, vac.data(), 4ull * nvac);
+  MoveArgs a{};
+  a.count = count;
+  a.nvac = nvac;
+  a.vac_szx = h->mv_in;
+  a.vac_trx = h->mv_in + nvac;
+  a.src = reinterpret_cast<const uint32_t*>(h->mv_in + 2ull * nvac);
+  a.dst = a.src + count;
+  a.vac = a.dst + count;
+  a.stage = h->mv_stage;
+  a.peer = h->peer;
+  a.jobs = h->mv_jobs;
+  a.ctr = h->mv_ctr;
+  a.rstage = h->mv_rstage;
+  hipStream_t st = h->stream;
+  HB_CHECK(hipMemcpyAsync(h->mv_in, h->mv_host.data(), in_words * 8, hipMemcpyHostToDevice, st));
+  HB_CHECK(hipMemsetAsync(h->mv_ctr, 0, 16, st));
+  hipLaunchKernelGGL(k_move_gather, dim3((count + 255) / 256), dim3(256), 0, st, h->st, a);
+  HB_CHECK(hipGetLastError());
+  // how many windows travel (none after a reset, the usual case: no ring kernels then)
+  unsigned long long ctr[2] = {0, 0};
+  HB_CHECK(hipMemcpyAsync(ctr, h->mv_ctr, 16, hipMemcpyDeviceToHost, st));
+  HB_CHECK(hipStreamSynchronize(st));
+  const uint32_t njobs = (uint32_t)ctr[0];
+  if (njobs) {
+    if (ctr[0] > (uint64_t)h->nmax * count || ctr[1] > ctr[0] * h->W) return HB_EINVARIANT;
+    rc = mv_grow(reinterpret_cast<void**>(&h->mv_rstage), &h->mv_rstage_cap, ctr[1]);
+    if (rc != HB_OK) return rc;
+    a.rstage = h->mv_rstage;
+    hipLaunchKernelGGL(k_move_ring<false>, dim3((njobs + 3) / 4), dim3(256), 0, st, h->st, a, njobs);
+    HB_CHECK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_move_scatter, dim3((count + nvac + 255) / 256), dim3(256), 0, st, h->st, a);
+  HB_CHECK(hipGetLastError());
+  if (njobs) {
+    hipLaunchKernelGGL(k_move_ring<true>, dim3((njobs + 3) / 4), dim3(256), 0, st, h->st, a, njobs);
+    HB_CHECK(hipGetLastError());
+  }
+  HB_CHECK(hipStreamSynchronize(st));
+  // the host mirrors of the extent words follow
+  for (int kind = 0; kind < (sized ? 2 : 1); ++kind) {
+    std::vector<uint64_t>& hx = kind ? h->h_szx : h->h_trx;
+    std::vector<uint64_t> moved(count);
+    for (uint32_t i = 0; i < count; ++i) moved[i] = hx[src[i]];
+    for (uint32_t v = 0; v < nvac; ++v) hx[vac[v]] = h->mv_host[(kind ? 0 : nvac) + v];
+    for (uint32_t i = 0; i < count; ++i) hx[dst[i]] = moved[i];
+  }
   return HB_OK;
 }
 

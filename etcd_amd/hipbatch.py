@@ -105,6 +105,7 @@ def lib():
         "hb_load_groups": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_void_p]),
         "hb_get_groups": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_void_p]),
         "hb_remove_groups": (C.c_int, [H, C.c_uint32, C.c_uint32]),
+        "hb_move_groups": (C.c_int, [H, C.c_uint32, C.c_void_p, C.c_void_p]),
         "hb_set_inflights": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
         "hb_set_log_bounds": (C.c_int, [H, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
         "hb_load_entry_sizes": (C.c_int, [H, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -219,6 +220,15 @@ class Engine:
 
     def remove_groups(self, first, count):
         _check("hb_remove_groups", lib().hb_remove_groups(self.h, first, count))
+
+    def move_groups(self, src, dst):
+        """hb_move_groups: slot dst[i] takes every device word of slot src[i] (all sources
+        are read first: swaps, cycles and chains are fine); vacated slots end up empty."""
+        s = np.ascontiguousarray(src, dtype=np.uint32)
+        d = np.ascontiguousarray(dst, dtype=np.uint32)
+        assert s.shape == d.shape and s.ndim == 1
+        _check("hb_move_groups", lib().hb_move_groups(self.h, len(s), s.ctypes.data if len(s) else None,
+                                                      d.ctypes.data if len(d) else None))
 
     def set_inflights(self, group, slot, start, vals):
         v = np.ascontiguousarray(vals, dtype=np.uint64)

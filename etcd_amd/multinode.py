@@ -35,6 +35,8 @@ HBN_ECOMPACTED = -20
 HBN_EUNAVAILABLE = -21
 HBN_ESNAPOUTOFDATE = -22
 HBN_FAULT_DOUBLE_CONF = 32
+HBN_PLACE_ARRIVAL = 0  # a group keeps the free slot it got when it was created (the default)
+HBN_PLACE_ROLE = 1  # led groups in one dense slot range, the others in the next (hbn_set_placement)
 
 EntryNormal, EntryConfChange = 0, 1
 ConfChangeAddNode, ConfChangeRemoveNode, ConfChangeUpdateNode = 0, 1, 2
@@ -81,6 +83,11 @@ class hbn_group_status(C.Structure):
 
 class hbn_config(C.Structure):
     _fields_ = [("election_tick", C.c_uint32), ("heartbeat_tick", C.c_uint32), ("applied", C.c_uint64)]
+
+
+class hbn_placement(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("led", C.c_uint32), ("other", C.c_uint32), ("mixed_tiles", C.c_uint32),
+                ("moves_total", C.c_uint64), ("repacks", C.c_uint64)]
 
 
 class RaftPanic(RuntimeError):
@@ -215,6 +222,8 @@ def lib():
             "hbn_advance": (C.c_int, [vp, P(u64), u64]),
             "hbn_status": (C.c_int, [vp, u64, P(hbn_group_status)]),
             "hbn_engine": (vp, [vp]),
+            "hbn_set_placement": (C.c_int, [vp, u32]),
+            "hbn_placement_stats": (C.c_int, [vp, P(hbn_placement)]),
             # include/hbroute.h: owner routing across a node's GPUs (etcd_amd/shard.py NativeRouter)
             "hbn_owner": (u32, [u64, u32]),
             "hbn_router_create": (C.c_int, [vp, u64, u32, u32, P(vp)]),
@@ -535,6 +544,17 @@ class MultiNode:
         ids = list(rds)
         arr = (C.c_uint64 * max(1, len(ids)))(*ids)
         _check("hbn_advance", lib().hbn_advance(self.p, arr, len(ids)))
+
+    def SetPlacement(self, mode):
+        """HBN_PLACE_ARRIVAL / HBN_PLACE_ROLE (hbn_set_placement): which device slots the groups
+        occupy.  Unobservable in Ready / Status; ROLE re-packs now and at every Advance."""
+        _check("hbn_set_placement", lib().hbn_set_placement(self.p, mode))
+
+    def PlacementStats(self):
+        """hbn_placement_stats as a dict: mode, led, other, mixed_tiles, moves_total, repacks."""
+        s = hbn_placement()
+        _check("hbn_placement_stats", lib().hbn_placement_stats(self.p, C.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in hbn_placement._fields_}
 
     def Status(self, group):
         s = hbn_group_status()

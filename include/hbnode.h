@@ -255,6 +255,40 @@ int hbn_status(hbn_node* n, uint64_t group, hbn_group_status* out);         /* :
 /* The device handle underneath (statistics, profiling). */
 hb_handle* hbn_engine(hbn_node* n);
 
+/* ---- slot placement ---------------------------------------------------------
+ * Which device slot a group occupies.  Placement is unobservable through this
+ * API (Ready content, Status and faults are the same under both modes; the
+ * order of groups within a Ready is unspecified either way); it decides only
+ * which groups share the 64-byte lines of the device's [slot][G] arrays.
+ *   HBN_PLACE_ARRIVAL  a group takes a free slot when it is created and keeps it
+ *                      for life (the default).
+ *   HBN_PLACE_ROLE     the led groups (raft_state == leader) occupy one dense
+ *                      slot range [0, led) and every other live group the
+ *                      adjacent dense range [led, led + other), so at most one
+ *                      64-slot aligned tile holds groups of both kinds.  This
+ *                      holds when hbn_set_placement returns and when every later
+ *                      hbn_advance returns: both re-pack the map on the calling
+ *                      thread, after the pending device step and loads, with one
+ *                      hb_move_groups call that moves at most 2 x (groups whose
+ *                      led / not-led role changed since the last re-pack + groups
+ *                      removed since) groups (the first re-pack after switching
+ *                      the mode on may move every group).  Between re-packs a new
+ *                      group sits above the other range, RemoveGroup leaves a
+ *                      hole and a role change leaves the group where it is.
+ * Groups without peers have no device slot and are outside the map.
+ * HB_EINVAL: NULL node, unknown mode. */
+#define HBN_PLACE_ARRIVAL 0
+#define HBN_PLACE_ROLE    1
+int hbn_set_placement(hbn_node* n, uint32_t mode);
+/* mode; the live groups with a device slot that are led / not led (the host
+ * view) and the 64-slot aligned tiles that hold both kinds, as of now; the
+ * groups moved by and the number of re-packs since hbn_start. */
+typedef struct hbn_placement {
+  uint32_t mode, led, other, mixed_tiles;
+  uint64_t moves_total, repacks;
+} hbn_placement;
+int hbn_placement_stats(hbn_node* n, hbn_placement* out);
+
 #ifdef __cplusplus
 }
 #endif

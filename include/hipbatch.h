@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define HB_ABI_VERSION 5
+#define HB_ABI_VERSION 6
 
 /* ---- error codes -------------------------------------------------------- */
 #define HB_OK          0
@@ -400,6 +400,29 @@ int  hb_get_groups(hb_handle* h, uint32_t first, uint32_t count, hb_group* out);
 /* RemoveGroup (raft/multinode.go:219-222): mark slots empty (all messages to
  * them are ignored until reloaded). */
 int  hb_remove_groups(hb_handle* h, uint32_t first, uint32_t count);
+/* Relocate groups on the device (compacting, defragmenting or re-ordering the
+ * slot space; libhbnode's role-ordered placement, hbn_set_placement).
+ * Slot dst[i] takes everything the handle keeps for slot src[i], as it was before the call.
+ * src[] are distinct; dst[] are distinct; src[i] == dst[i] is a no-op pair.
+ * A swap is {a,b} -> {b,a}; cycles and chains are allowed.
+ * Slots in src but not in dst end up empty, as after hb_remove_groups.
+ * A dst slot that is not in src loses what it held.
+ * src and dst are host arrays.
+ * Ordered on the apply stream like hb_load_groups (synchronous).
+ * Events already produced keep the old slot numbers.
+ * "Everything" is the raw device state, not an hb_group round trip: the group
+ * record and every Progress in whatever lazy form the device keeps them, the
+ * timers (elapsed, rand_pos, election / heartbeat ticks), the peer ids of
+ * hb_load_peers, each follower's live inflight window at its ring positions,
+ * and both log-index rings with their content: hb_log_capacity(dst[i])
+ * afterwards is what hb_log_capacity(src[i]) was.  The ring extents of the
+ * overwritten slots pass to the vacated ones, so every slot still owns one of
+ * each kind and repeated moves do not grow the log pool.  All sources are read
+ * before any destination is written (staging buffers grown on demand and
+ * reused: no device allocation per call in steady state).
+ * HB_EINVAL, before any device work: a NULL handle, count > 0 with a NULL
+ * array, a slot >= capacity, a duplicate in src, a duplicate in dst. */
+int  hb_move_groups(hb_handle* h, uint32_t count, const uint32_t* src, const uint32_t* dst);
 /* The application changed a group's Storage (MemoryStorage.Compact /
  * CreateSnapshot / ApplySnapshot, raft/storage.go:150-214): refresh the
  * device copies of raftLog.firstIndex() and raftLog.snapshot().Metadata.Index

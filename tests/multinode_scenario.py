@@ -1,0 +1,158 @@
+"""The randomised MultiNode-vs-oracle scenario of
+tests/test_multinode_gpu.py::test_random_multinode_vs_oracle (96 groups in
+capacity 128, 60 rounds of Campaign / Propose / responses / reports / Tick, one
+oracle raft per group, every Ready checked against the oracle), restated as a
+function with two hooks so that other tests can run it under a different node
+setup and look at the node after every Advance.  The per-round Ready assertions
+are the same as in that test.
+"""
+import numpy as np
+
+from etcd_amd import abi
+from etcd_amd.multinode import (Config, HardState, MemoryStorage, Message, SoftState, StartMultiNode, StateLeader,
+                                emptyState)
+
+from .test_multinode_gpu import _dev_msgs, _orc_msgs
+
+G, ROUNDS, CAPACITY = 96, 60, 128
+
+
+def run_random_scenario(seed, n, setup=None, after_advance=None):
+    """setup(mn): called on the fresh node before any group exists.
+    after_advance(mn, st, gids, rnd): called after every Advance; st[gid]["o"] is
+    the group's oracle raft, st[gid].get("dead") says its oracle faulted.
+    Returns (mn, st, gids, seen)."""
+    from oracle.pyoracle import Msg, Raft
+    rng = np.random.default_rng(seed)
+    seen = dict(app_ents=0, leaders=0, commits=0, votes=0, beats=0)
+    peers = list(range(1, n + 1))
+    draws = rng.integers(0, 1 << 62, 1 << 14, dtype=np.uint64)
+    mn = StartMultiNode(1, capacity=CAPACITY, max_replicas=n, max_inflight=8)
+    if setup is not None:
+        setup(mn)
+    mn.SetRand(draws)
+    gids = [1000 + 17 * g for g in range(G)]
+    st = {}
+    for gid in gids:
+        s = MemoryStorage()
+        mn.CreateGroup(gid, Config(election=3, heartbeat=1), s, peers=peers)
+        o = Raft(1, peers, ents=[(i, 1) for i in range(1, n + 1)], max_inflight=8,
+                 election=3, heartbeat=1, draws=draws)
+        o.r.Term = 1
+        o.r.log.committed = n
+        assert o.Commit == 0
+        st[gid] = dict(s=s, o=o, data={}, applied=0, prev_hard=(1, 0, 0), prev_soft=(0, 0), seq=0)
+    for rnd in range(ROUNDS):
+        for gid in gids:
+            d, o = st[gid], st[gid]["o"]
+            if d.get("dead"):
+                continue
+            for _ in range(int(rng.integers(0, 4))):
+                if o.fault:
+                    break
+                a = rng.random()
+                frm = int(rng.integers(1, n + 2))  # n + 1 is a non-member
+                member = frm <= n
+                if a < 0.12 and (o.state != abi.HB_STATE_LEADER or rng.random() < 0.05):
+                    mn.Campaign(gid)  # a leader's campaign panics (raft/raft.go:396): both report it
+                    o.Step(Msg(abi.HB_MSG_HUP))
+                elif a < 0.30:
+                    d["seq"] += 1
+                    data = f"{gid}-{d['seq']}".encode()
+                    mn.Propose(gid, data)
+                    o.Step(Msg(abi.HB_MSG_PROP, From=1, Entries=1))
+                    d.setdefault("props", []).append(data)
+                elif a < 0.45:
+                    term = o.Term + (1 if rng.random() < 0.03 else 0)
+                    rej = bool(rng.random() < 0.3)
+                    mn.Step(gid, Message(Type=abi.HB_MSG_VOTE_RESP, From=frm, Term=term, Reject=rej))
+                    if member:
+                        o.Step(Msg(abi.HB_MSG_VOTE_RESP, From=frm, Term=term, Reject=rej))
+                elif a < 0.80:
+                    rej = bool(rng.random() < 0.15)
+                    idx = int(rng.integers(0, o.lastIndex + 1))
+                    hint = int(rng.integers(0, o.lastIndex + 1))
+                    mn.Step(gid, Message(Type=abi.HB_MSG_APP_RESP, From=frm, Term=o.Term, Index=idx, Reject=rej,
+                                         RejectHint=hint))
+                    if member:
+                        o.Step(Msg(abi.HB_MSG_APP_RESP, From=frm, Term=o.Term, Index=idx, Reject=rej,
+                                   RejectHint=hint))
+                elif a < 0.92:
+                    mn.Step(gid, Message(Type=abi.HB_MSG_HEARTBEAT_RESP, From=frm, Term=o.Term))
+                    if member:
+                        o.Step(Msg(abi.HB_MSG_HEARTBEAT_RESP, From=frm, Term=o.Term))
+                elif a < 0.97:
+                    mn.ReportUnreachable(frm, gid)
+                    if member:
+                        o.Step(Msg(abi.HB_MSG_UNREACHABLE, From=frm))
+                elif member and frm != 1 and o.state == abi.HB_STATE_LEADER and \
+                        o.pr(frm).State == abi.HB_PR_SNAPSHOT:
+                    fail = bool(rng.random() < 0.5)
+                    mn.ReportSnapshot(frm, gid, fail)
+                    o.Step(Msg(abi.HB_MSG_SNAP_STATUS, From=frm, Reject=fail))
+        if rnd % 5 == 4:
+            mn.Tick()
+            for gid in gids:
+                st[gid]["o"].tick()
+        rds = mn.Ready()
+        for gid in gids:
+            d, o = st[gid], st[gid]["o"]
+            if d.get("dead"):
+                continue
+            if o.fault:
+                assert gid in rds and rds[gid].fault == o.fault, f"group {gid}: fault"
+                d["dead"] = True
+                continue
+            om = _orc_msgs(o)
+            hard = (o.Term, o.Vote, o.Commit)  # r.HardState: r.Commit, not raftLog.committed
+            soft = (o.lead, o.state)
+            unstable_lo = d["s"].LastIndex() + 1
+            committed_lo = max(d["applied"] + 1, d["s"].FirstIndex())
+            want_any = bool(om) or hard != d["prev_hard"] or soft != d["prev_soft"] or \
+                o.lastIndex >= unstable_lo or o.committed >= committed_lo
+            ctx = f"seed {seed} round {rnd} group {gid}"
+            if not want_any:
+                assert gid not in rds, ctx
+                continue
+            rd = rds[gid]
+            assert rd.fault == 0, ctx
+            assert _dev_msgs(rd) == om, f"{ctx}: messages\n dev {_dev_msgs(rd)}\n ora {om}"
+            assert rd.HardState == (HardState(*hard) if hard != d["prev_hard"] else emptyState), ctx
+            assert rd.SoftState == (SoftState(*soft) if soft != d["prev_soft"] else None), ctx
+            assert [(e.Index, e.Term) for e in rd.Entries] == \
+                   [(i, o.term(i)) for i in range(unstable_lo, o.lastIndex + 1)], ctx
+            assert [(e.Index, e.Term) for e in rd.CommittedEntries] == \
+                   [(i, o.term(i)) for i in range(committed_lo, o.committed + 1)], ctx
+            # payloads: proposals in order, noops empty
+            for e in rd.Entries:
+                if e.Data is not None:
+                    d["data"][e.Index] = e.Data
+            for m in rd.Messages:
+                for e in m.Entries:
+                    if m.Type == abi.HB_MSG_APP and e.Data is not None:
+                        assert d["data"][e.Index] == e.Data, ctx
+            seen["app_ents"] += sum(1 for m in rd.Messages if m.Type == abi.HB_MSG_APP and m.Entries)
+            seen["votes"] += sum(1 for m in rd.Messages if m.Type == abi.HB_MSG_VOTE)
+            seen["beats"] += sum(1 for m in rd.Messages if m.Type == abi.HB_MSG_HEARTBEAT)
+            seen["commits"] += len(rd.CommittedEntries)
+            seen["leaders"] += int(rd.SoftState is not None and rd.SoftState.RaftState == StateLeader)
+            d["s"].Append(rd.Entries)
+            if rd.SoftState is not None:
+                d["prev_soft"] = soft
+            if rd.HardState != emptyState:
+                d["prev_hard"] = hard
+            if d["prev_hard"][2]:
+                d["applied"] = d["prev_hard"][2]
+        mn.Advance(rds)
+        if after_advance is not None:
+            after_advance(mn, st, gids, rnd)
+    assert min(seen.values()) > 0, seen  # every kind of Ready content was compared
+    # every accepted proposal's payload reached storage in proposal order
+    for gid in gids:
+        s = st[gid]["s"]
+        ents, err = s.Entries(n + 1, s.LastIndex() + 1) if s.LastIndex() > n else ([], None)
+        got = [e.Data for e in (ents or []) if e.Data is not None]
+        props = st[gid].get("props", [])
+        it = iter(props)
+        assert all(any(p == g for p in it) for g in got), f"group {gid}: payload order"
+    return mn, st, gids, seen
