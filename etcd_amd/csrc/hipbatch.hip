@@ -266,16 +266,13 @@ __device__ __forceinline__ uint32_t excl_scan256(uint32_t v, uint32_t* sh4, uint
 #define HB_HIST_TPB 4
 #endif
 constexpr uint32_t HIST_TPB = HB_HIST_TPB;
-// One-pass partitions take each tile's digit offsets without a scan launch
-// (HB_RDX_DIRECT): k_radix_hist also writes each workgroup's digit sums
+// One-pass partitions take each tile's digit offsets without a scan launch:
+// k_radix_hist also writes each workgroup's digit sums
 // (DirectSums::agg) and adds them into its superblock's (SB_HW workgroups,
 // agent-scope atomics), and the scatter sums the superblocks, aggregates and
 // tiles before its own (k_radix_scatter_d).  The superblock sums rotate over
 // three buffers: a step's hist clears the one the next step adds into (read
 // by the scatter two steps ago), as far as that one was dirtied.
-#ifndef HB_RDX_DIRECT
-#define HB_RDX_DIRECT 1
-#endif
 constexpr uint32_t SB_HW = 32;
 constexpr uint32_t SUP_BUFS = 3;
 struct DirectSums {
@@ -621,7 +618,7 @@ __global__ void __launch_bounds__(RDX_THREADS) __attribute__((amdgpu_waves_per_e
                                     blockIdx.x == 0);
 }
 
-// One pass with direct offsets (HB_RDX_DIRECT): each tile's exclusive digit
+// One pass with direct offsets: each tile's exclusive digit
 // prefix = the superblocks before its own + the hist workgroups before its own
 // in the superblock + the tiles before it in its hist workgroup; the digit
 // totals = every superblock.  Four lanes per digit split those loads, all
@@ -867,11 +864,11 @@ struct ApplyArgs {
   // X mode (follower-side batches): the records' extensions {hint, commit}
   const uint4* recx;        // beside rec (k_route input)
   uint4* slotx;             // [kmax][G] beside slot (null: no X mode this step)
-  // storm hand-over (n >= 5, HB_ROUTE_STORM): k_route closes a partition whose
-  // groups with messages are all busy leaders with a higher-term message, as
-  // k_apply_lead would (flags, lists, event chunks), and k_apply_lead skips it
+  // storm hand-over (n >= 5): k_route closes a partition none of whose groups
+  // k_apply_lead would load (handover_class), as k_apply_lead would (flags,
+  // lists, event chunks), runs k_elect's lane over it, and k_apply_lead skips it
   uint32_t nmax;            // the handle's replica bound (5 or 7)
-  uint32_t storm;           // 1: this step's route may close partitions (lskip), 2: and run k_elect's lane there
+  uint32_t storm;           // 2: this step's route closes such partitions (lskip), 0: it does not
   uint8_t* lskip;           // [NB] 1: the route closed the partition
 };
 
@@ -911,15 +908,12 @@ enum { ST_MSGS, ST_APPRESP, ST_VOTERESP, ST_DROPPED, ST_COMMITS, ST_WON, ST_LOST
 constexpr uint32_t FLAG_WORDS = PART / 32;  // per-partition bitmask of groups handed to k_apply
 // Set (or clear) lane `lane`'s bit of a partition flag mask.  `lane & 63` must
 // be the hardware lane and `lane >> 6` the wave's slot in the partition, so a
-// wave owns words 2w and 2w + 1.  With HB_FLAG_BALLOT the wave ballots the
-// predicate and its lowest active lane issues at most two LDS atomics, instead
-// of one per flagged lane all landing on the same word (32-way serialised).
-#ifndef HB_FLAG_BALLOT
-#define HB_FLAG_BALLOT 1
-#endif
+// wave owns words 2w and 2w + 1.  The wave ballots the predicate and its
+// lowest active lane issues at most two LDS atomics, instead of one per
+// flagged lane all landing on the same word (32-way serialised; per-lane
+// atomics measured 0.4533 vs 0.4516 ms on cfg3).
 template <bool SET>
 __device__ __forceinline__ void flag_put(uint32_t* words, uint32_t lane, bool on) {
-#if HB_FLAG_BALLOT
   const uint64_t act = __ballot(1);
   const uint64_t b = __ballot(on);
   if (b && (lane & 63) == (uint32_t)__ffsll((long long)act) - 1) {
@@ -927,9 +921,6 @@ __device__ __forceinline__ void flag_put(uint32_t* words, uint32_t lane, bool on
     if (lo) SET ? atomicOr(&words[w], lo) : atomicAnd(&words[w], ~lo);
     if (hi) SET ? atomicOr(&words[w + 1], hi) : atomicAnd(&words[w + 1], ~hi);
   }
-#else
-  if (on) SET ? atomicOr(&words[lane >> 5], 1u << (lane & 31)) : atomicAnd(&words[lane >> 5], ~(1u << (lane & 31)));
-#endif
 }
 constexpr uint32_t KPL = 64;                // bucket key bytes scanned per lane per segment
 constexpr uint32_t SEG = PART * KPL;        // positions per key-scan segment
@@ -1224,22 +1215,35 @@ constexpr uint32_t ROUTE_THREADS = 1024;
 // leader there proposes, and one without the flag is loaded and stepped up to
 // the higher term, as before)
 constexpr uint32_t CNT_MASK = 0x7F, CNT_HIGHER = 0x80;
-// HB_ROUTE_SORTED=1: the route writes a group's slots in arrival order when
-// they hold all its messages (a sort of the <= KMAX arrival indices per group
-// in the write-out), so k_apply_lead reads slot x for message x straight from
-// HBM instead of staging all slots in LDS to sort them (32 KB per workgroup at
-// n = 5: 4 waves/SIMD instead of 3 with HB_LEAD_WAVES=4).  Measured (r05,
-// same box): cfg3 0.457-0.460 vs 0.461-0.463 ms, follow n = 5 lane 66.4 vs
-// 71.7 us but its step 0.193 vs 0.190 ms and cfg4 1.912 vs 1.871 ms (the
-// route's sort): off.
-#ifndef HB_ROUTE_SORTED
-#define HB_ROUTE_SORTED 0
-#endif
+// The storm hand-over rule: what k_apply_lead does with a group, in a step
+// without dense proposals and without X, before it steps any of its messages.
+// k_route closes a partition whose groups with messages are all HO_NONE,
+// HO_ELECT or HO_APPLY, and k_apply_lead then skips it (lskip), so the two
+// must agree group for group: both call this.
+//   not live (removed or faulted)      HO_NONE   nothing to do
+//   no leader                          HO_ELECT  handed over unloaded, k_elect's
+//   leader, r.Commit unknown (M_NC)    HO_APPLY  handed over unloaded, not k_elect's
+//   leader, c <= nmax - 1              HO_LOAD   loaded and stepped
+//   leader, nmax - 1 < c <= cap        HO_ELECT  with `higher` (an election storm's leader),
+//                                      HO_LOAD   without
+//   leader, c > cap                    HO_OVER   handed over unloaded to k_apply (its bucket
+//                                                walk); the route keeps such a partition open
+// mlo: meta's low word; c: the group's messages in the batch; higher: one of
+// its slotted messages carries a Term above the group's (the route's hib,
+// CNT_HIGHER); cap: the slots a group keeps.
+enum : uint32_t { HO_NONE, HO_LOAD, HO_ELECT, HO_APPLY, HO_OVER };
+__device__ __forceinline__ uint32_t handover_class(uint32_t mlo, uint32_t c, bool higher, uint32_t nmax, uint32_t cap) {
+  if (m_n(mlo) == 0 || m_fault(mlo) != 0) return HO_NONE;
+  if (m_state(mlo) != HB_STATE_LEADER) return HO_ELECT;
+  if (mlo & (uint32_t)M_NC) return HO_APPLY;
+  if (c > cap) return HO_OVER;
+  return (c > nmax - 1 && higher) ? HO_ELECT : HO_LOAD;
+}
+// (The route writes a group's slots in counter-rank order; sorting them by
+// arrival in its write-out, so that k_apply_lead needs no LDS slot copy,
+// measured cfg4 1.912 vs 1.871 ms for the sort.)
 #ifndef HB_ROUTE_UNROLL
 #define HB_ROUTE_UNROLL 4
-#endif
-#ifndef HB_ROUTE_STORM
-#define HB_ROUTE_STORM 1
 #endif
 constexpr uint32_t ROUTE_UNROLL = HB_ROUTE_UNROLL;  // records in flight per lane
 // Route groups per workgroup (log2), measured on MI355X with 16-byte records
@@ -1256,8 +1260,10 @@ template <int KMAX, bool X> struct RouteGeom {
   // workgroups per bucket: 2^(PART_LOG + sis_log - RG_LOG) (sis_log >= RG_LOG - PART_LOG)
 };
 
-// EN > 0 (n = EN, storm mode 2): the election lane runs in the route's
-// workgroup over the partitions it closes, from the LDS slots (§3.2)
+// EN > 0 (n = EN, a step with ApplyArgs::storm): the storm hand-over — the
+// route closes the partitions k_apply_lead would only hand over
+// (handover_class) and runs the election lane over them in its own
+// workgroup, from the LDS slots (§3.2).  EN = 0 carries none of it.
 template <int KMAX, bool X, int EN = 0>
 __global__ void __launch_bounds__(ROUTE_THREADS) k_route(ApplyArgs a) {
   using RGm = RouteGeom<KMAX, X>;
@@ -1268,14 +1274,11 @@ __global__ void __launch_bounds__(ROUTE_THREADS) k_route(ApplyArgs a) {
   __shared__ uint4 l_slotx[X ? KMAX : 1][X ? RG : 1];  // X mode: their extensions
   __shared__ uint32_t l_ptot[NP];
   constexpr bool HI = KMAX >= 5;  // (CNT_HIGHER)
-  constexpr bool ST = HI && !X && HB_ROUTE_STORM;
-  static_assert(!ST || RG % ROUTE_THREADS == 0, "the storm ballots run at loop level");
-  __shared__ uint32_t l_pf[ST ? RG / 32 : 1];  // groups k_apply_lead would hand over unloaded (pflag words)
-  __shared__ uint32_t l_ef[ST ? RG / 32 : 1];  // ... of them, k_elect's (eflag words)
-  __shared__ uint32_t l_ok[ST ? NP : 1];       // 1: the partition needs no k_apply_lead
-  constexpr bool EL = ST && EN > 0;
-  static_assert(!EL || (RG == ROUTE_THREADS && !HB_ROUTE_SORTED), "EL: one group per lane, slots as routed");
-  __shared__ uint64_t l_moff[EL ? NP : 1];      // EL: the partitions' M chunks
+  constexpr bool EL = EN > 0;  // (the host launches it only without props and X)
+  static_assert(!EL || (HI && !X && RG == ROUTE_THREADS), "EL: one group per lane");
+  __shared__ uint32_t l_pf[EL ? RG / 32 : 1];  // EL: groups k_apply_lead would hand over unloaded (pflag words)
+  __shared__ uint32_t l_ok[EL ? NP : 1];        // 1: the partition needs no k_apply_lead
+  __shared__ uint64_t l_moff[EL ? NP : 1];      // the partitions' M chunks
   __shared__ uint32_t l_efill[EL ? NP : 1];     // ... and their fill
   __shared__ uint64_t l_stats[EL ? ST_N + 1 : 1];
   // blockIdx -> (bucket, w): the W sisters of a bucket share blockIdx % 8 (one XCD)
@@ -1287,10 +1290,9 @@ __global__ void __launch_bounds__(ROUTE_THREADS) k_route(ApplyArgs a) {
   const uint32_t lg0 = w * RG;  // first group (in the bucket) of this workgroup
   // (uniform; a follower-side batch's route measured +12 us with it)
   const bool hi_on = HI && !X && !a.props_on;
-  const bool storm = ST && a.storm;  // (the host sets it only without props and X)
   for (uint32_t i = tid; i < RG; i += ROUTE_THREADS) l_cnt[i] = 0;
   if (tid < NP) l_ptot[tid] = 0;
-  if (ST && tid < NP) l_ok[tid] = 1;
+  if (EL && tid < NP) l_ok[tid] = 1;
   if (EL && tid < NP) l_efill[tid] = 0;
   if (EL && tid <= ST_N) l_stats[tid] = 0;
   __syncthreads();
@@ -1330,20 +1332,17 @@ __global__ void __launch_bounds__(ROUTE_THREADS) k_route(ApplyArgs a) {
   }
   __syncthreads();
   const uint32_t gbase = (bk << (PART_LOG + sl)) + lg0;
-  const bool el = EL && storm;            // slots written after the election lane (EL)
-  uint32_t e_c = 0;                       // (EL: the lane's group, i = tid)
+  uint32_t e_c = 0;  // (EL: the lane's group, i = tid)
   bool e_hand = false, e_elect = false;
   uint64_t e_meta = 0;
   for (uint32_t i = tid; i < RG; i += ROUTE_THREADS) {
     const uint32_t c = l_cnt[i], g = gbase + i;
-    bool hand = false, elect = false, ok = true;  // (storm)
+    bool hand = false, elect = false, ok = true;  // (EL)
     if (g < G) {
       // a group whose messages all sit in its slots: any Term above its own?
       bool hib = false;
       uint64_t meta = 0;
-      if (storm && c > 0)
-        meta = EL ? a.S.meta[g] : (uint64_t)at32(reinterpret_cast<const uint32_t*>(a.S.meta), 2 * g);
-      const uint32_t mlo = (uint32_t)meta;
+      if (EL && c > 0) meta = a.S.meta[g];
       if (hi_on && c <= (uint32_t)KMAX) {
         const uint64_t t = a.S.term[g];
 #pragma unroll
@@ -1357,54 +1356,25 @@ __global__ void __launch_bounds__(ROUTE_THREADS) k_route(ApplyArgs a) {
         }
       }
       a.cnt[g] = (uint8_t)((c < CNT_MASK ? c : CNT_MASK) | (hib ? CNT_HIGHER : 0u));
-      if (storm && c > 0) {
-        // what k_apply_lead (no proposals, no X) hands over unloaded at message 0:
-        // a live group that is no leader, a leader whose r.Commit is unknown
-        // (M_NC), and a busy leader (more messages than n - 1, all in its slots)
-        // with a higher-term message (busy_hi); k_elect tries all but M_NC leaders
-        const bool live = m_n(mlo) != 0 && m_fault(mlo) == 0;
-        const bool leader = m_state(mlo) == HB_STATE_LEADER, nc = (mlo & (uint32_t)M_NC) != 0;
-        const bool busy_hi = leader && !nc && c > a.nmax - 1 && c <= (uint32_t)KMAX && hib;
-        hand = live && (!leader || nc || busy_hi);
-        elect = live && (!leader || busy_hi);
-        ok = !live || hand;  // (a leader to step: k_apply_lead runs the partition)
-        if (hand) a.resume[g] = 1u << 30;
-      }
-      if constexpr (EL) {
+      if constexpr (EL) {  // (the slots are written after the election lane)
+        if (c > 0) {  // (a group k_apply_lead would load, or hand to k_apply's bucket walk, keeps the partition open)
+          const uint32_t cls = handover_class((uint32_t)meta, c, hib, a.nmax, (uint32_t)KMAX);
+          elect = cls == HO_ELECT;
+          hand = elect || cls == HO_APPLY;
+          ok = hand || cls == HO_NONE;
+          if (hand) a.resume[g] = 1u << 30;
+        }
         e_c = c;
         e_hand = hand;
         e_elect = elect;
         e_meta = meta;
-      }
-      // arrival order of a group whose messages all fit (odd-even transposition
-      // over the arrival indices, slot numbers riding along as nibbles)
-      uint32_t perm = 0, key[KMAX];
+      } else {
 #pragma unroll
-      for (uint32_t k = 0; k < (uint32_t)KMAX; ++k) {
-        perm |= k << (4 * k);
-        key[k] = (HB_ROUTE_SORTED && k < c && c <= (uint32_t)KMAX) ? l_slot[k][i].y : 0xFFFFFFFFu;
-      }
-      if (HB_ROUTE_SORTED && c > 1 && c <= (uint32_t)KMAX) {
-#pragma unroll
-        for (uint32_t r = 0; r < (uint32_t)KMAX; ++r) {
-#pragma unroll
-          for (uint32_t k = (r & 1); k + 1 < (uint32_t)KMAX; k += 2) {
-            const uint32_t k0 = key[k], k1 = key[k + 1];
-            const bool sw = k1 < k0;
-            key[k] = sw ? k1 : k0;
-            key[k + 1] = sw ? k0 : k1;
-            const uint32_t p0 = (perm >> (4 * k)) & 0xF, p1 = (perm >> (4 * (k + 1))) & 0xF;
-            const uint32_t swp = (perm & ~(0xFFu << (4 * k))) | (p1 << (4 * k)) | (p0 << (4 * (k + 1)));
-            perm = sw ? swp : perm;
+        for (uint32_t k = 0; k < (uint32_t)KMAX; ++k) {
+          if (k < c) {
+            at32(a.slot, k * G + g) = l_slot[k][i];
+            if constexpr (X) at32(a.slotx, k * G + g) = l_slotx[k][i];
           }
-        }
-      }
-#pragma unroll
-      for (uint32_t k = 0; k < (uint32_t)KMAX; ++k) {
-        if (k < c && !el) {
-          const uint32_t src = (perm >> (4 * k)) & 0xF;
-          at32(a.slot, k * G + g) = l_slot[src][i];
-          if constexpr (X) at32(a.slotx, k * G + g) = l_slotx[src][i];
         }
       }
     }
@@ -1412,16 +1382,12 @@ __global__ void __launch_bounds__(ROUTE_THREADS) k_route(ApplyArgs a) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
     if ((tid & 63) == 0 && s) atomicAdd(&l_ptot[i >> PART_LOG], s);
-    if constexpr (ST) {
-      if (storm) {
-        const uint64_t b = __ballot(hand), e = __ballot(elect), bad = __ballot(!ok);
-        if ((tid & 63) == 0) {
-          l_pf[i >> 5] = (uint32_t)b;
-          l_pf[(i >> 5) + 1] = (uint32_t)(b >> 32);
-          l_ef[i >> 5] = (uint32_t)e;
-          l_ef[(i >> 5) + 1] = (uint32_t)(e >> 32);
-          if (bad) atomicAnd(&l_ok[i >> PART_LOG], 0u);
-        }
+    if constexpr (EL) {
+      const uint64_t b = __ballot(hand), bad = __ballot(!ok);
+      if ((tid & 63) == 0) {
+        l_pf[i >> 5] = (uint32_t)b;
+        l_pf[(i >> 5) + 1] = (uint32_t)(b >> 32);
+        if (bad) atomicAnd(&l_ok[i >> PART_LOG], 0u);
       }
     }
   }
@@ -1437,101 +1403,90 @@ __global__ void __launch_bounds__(ROUTE_THREADS) k_route(ApplyArgs a) {
     }
   }
   if constexpr (EL) {
-    if (el) {  // ---- the election lane over the closed partitions (k_elect's work, slots from LDS)
-      __syncthreads();  // l_moff
-      const uint32_t p = __builtin_amdgcn_readfirstlane(tid >> PART_LOG);
-      const uint32_t g = gbase + tid;
-      const bool closed = l_ok[p] != 0;  // (uniform per wave)
-      bool done = false;
-      uint32_t st_msgs = 0, st_app = 0, st_vote = 0, st_drop = 0, st_commit = 0;
-      ElectLane<EN> L;
-      L.won = L.lost = L.nev = 0;
-      L.committed = L.last = 0;
-      uint64_t last0 = 0;
-      if (closed) {
-        L.S = a.S;
-        L.E.chunk = a.ev + l_moff[p];
-        L.E.fill = &l_efill[p];
-        L.g = g;
-        L.meta = e_meta;
-        // k_elect's own groups: no leader, or a busy leader with a higher-term message (resume 0, not loaded)
-        const bool mine = e_elect && e_c <= (uint32_t)KMAX && L.self() < L.n() && !(L.meta & M_NC);
-        if (mine) {
-          L.load();
-          last0 = L.last;
-          const uint64_t commit0 = L.committed;
-          uint32_t key[KMAX];
+    // ---- the election lane over the closed partitions (k_elect's work, slots from LDS)
+    __syncthreads();  // l_moff
+    const uint32_t p = __builtin_amdgcn_readfirstlane(tid >> PART_LOG);
+    const uint32_t g = gbase + tid;
+    const bool closed = l_ok[p] != 0;  // (uniform per wave)
+    bool done = false;
+    uint32_t st_msgs = 0, st_app = 0, st_vote = 0, st_drop = 0, st_commit = 0;
+    ElectLane<EN> L;
+    L.won = L.lost = L.nev = 0;
+    L.committed = L.last = 0;
+    uint64_t last0 = 0;
+    if (closed) {
+      L.S = a.S;
+      L.E.chunk = a.ev + l_moff[p];
+      L.E.fill = &l_efill[p];
+      L.g = g;
+      L.meta = e_meta;
+      // k_elect's own groups: no leader, or a busy leader with a higher-term message (resume 0, not loaded)
+      const bool mine = e_elect && e_c <= (uint32_t)KMAX && L.self() < L.n() && !(L.meta & M_NC);
+      if (mine) {
+        L.load();
+        last0 = L.last;
+        const uint64_t commit0 = L.committed;
+        uint32_t key[KMAX];
 #pragma unroll
-          for (uint32_t k = 0; k < (uint32_t)KMAX; ++k) key[k] = k < e_c ? l_slot[k][tid].y : 0xFFFFFFFFu;
-          const uint32_t perm = arrival_perm<(uint32_t)KMAX>(key);
-          uint32_t x = 0;
+        for (uint32_t k = 0; k < (uint32_t)KMAX; ++k) key[k] = k < e_c ? l_slot[k][tid].y : 0xFFFFFFFFu;
+        const uint32_t perm = arrival_perm<(uint32_t)KMAX>(key);
+        uint32_t x = 0;
 #pragma nounroll
-          for (; x < e_c; ++x) {
-            uint32_t inf, org;
-            uint64_t mterm, ix;
-            slot_unpack(l_slot[(perm >> (4 * x)) & 0xF][tid], a.side, &inf, &org, &mterm, &ix);
-            const uint32_t type = inf & 0xF, from = (inf >> 4) & 0xF;
-            if (from >= L.n() && is_response(type)) {  // raft/multinode.go:235
-              st_drop++;
-              continue;
-            }
-            if (!L.takes(type, from, mterm)) break;
-            L.step(type, from, mterm, (inf >> 8) & 1u);
-            st_msgs++;
-            st_app += type == HB_MSG_APP_RESP;
-            st_vote += type == HB_MSG_VOTE_RESP;
+        for (; x < e_c; ++x) {
+          uint32_t inf, org;
+          uint64_t mterm, ix;
+          slot_unpack(l_slot[(perm >> (4 * x)) & 0xF][tid], a.side, &inf, &org, &mterm, &ix);
+          const uint32_t type = inf & 0xF, from = (inf >> 4) & 0xF;
+          if (from >= L.n() && is_response(type)) {  // raft/multinode.go:235
+            st_drop++;
+            continue;
           }
-          if (x > 0) {
-            L.store();
-            if (x == e_c) {
-              done = true;  // the group's batch ends here
-            } else {        // k_apply resumes at message x, loading what was stored
-              a.resume[g] = x;
-              a.commit0[g] = commit0;
-            }
-          }
-          st_commit = done && L.committed != commit0;
+          if (!L.takes(type, from, mterm)) break;
+          L.step(type, from, mterm, (inf >> 8) & 1u);
+          st_msgs++;
+          st_app += type == HB_MSG_APP_RESP;
+          st_vote += type == HB_MSG_VOTE_RESP;
         }
-        flag_put<false>(&l_pf[p * FLAG_WORDS], tid & (PART - 1), done);
+        if (x > 0) {
+          L.store();
+          if (x == e_c) {
+            done = true;  // the group's batch ends here
+          } else {        // k_apply resumes at message x, loading what was stored
+            a.resume[g] = x;
+            a.commit0[g] = commit0;
+          }
+        }
+        st_commit = done && L.committed != commit0;
       }
-      // the slots k_apply (or k_apply_lead / k_elect of an open partition) reads
-      if (g < G && e_c > 0 && (!closed || (e_hand && !done))) {
-#pragma unroll
-        for (uint32_t k = 0; k < (uint32_t)KMAX; ++k)
-          if (k < e_c) at32(a.slot, k * G + g) = l_slot[k][tid];
-      }
-      const uint32_t vals[ST_N + 1] = {st_msgs, st_app, st_vote, st_drop, st_commit, L.won, L.lost, 0,
-                                       (uint32_t)(L.last - last0), L.nev};
-      reduce_stats(a, l_stats, vals);  // (ends with a barrier: l_pf and l_efill are final)
+      flag_put<false>(&l_pf[p * FLAG_WORDS], tid & (PART - 1), done);
     }
-  }
-  if constexpr (ST) {
-    if (storm) {  // close the partitions k_apply_lead would only hand over (its fast_close)
-      if (tid < NP * FLAG_WORDS) {
-        const uint32_t p = tid / FLAG_WORDS, j = tid % FLAG_WORDS, part = (bk << sl) + w * NP + p;
-        if (part < a.NB && l_ok[p]) {
-          a.pflag[(size_t)part * FLAG_WORDS + j] = l_pf[p * FLAG_WORDS + j];
-          if (!el) a.eflag[(size_t)part * FLAG_WORDS + j] = l_ef[p * FLAG_WORDS + j];
-        }
-      }
-      if (tid < NP) {
-        const uint32_t part = (bk << sl) + w * NP + tid;
-        if (part < a.NB) {
-          a.lskip[part] = (uint8_t)l_ok[tid];
-          if (l_ok[tid]) {
-            a.ev_off[2 * part] = (uint64_t)part * PART * a.ev_per_msg;
-            a.ev_counts[2 * part] = 0;
-            a.ev_counts[2 * part + 1] = EL ? l_efill[EL ? tid : 0] : 0u;
-            uint32_t any = 0, eany = 0;
+    // the slots k_apply (or k_apply_lead / k_elect of an open partition) reads
+    if (g < G && e_c > 0 && (!closed || (e_hand && !done))) {
 #pragma unroll
-            for (uint32_t j = 0; j < FLAG_WORDS; ++j) {
-              any |= l_pf[tid * FLAG_WORDS + j];
-              eany |= l_ef[tid * FLAG_WORDS + j];
-            }
-            const uint32_t xs = blockIdx.x & 7;  // (= the bucket's XCD slot, as k_apply_lead's)
-            if (any) a.ap_list[(size_t)xs * a.NB + atomicAdd(&a.ap_cnt[xs * CTR_STRIDE], 1u)] = part;
-            if (eany && !el) a.el_list[(size_t)xs * a.NB + atomicAdd(&a.el_cnt[xs * CTR_STRIDE], 1u)] = part;
-          }
+      for (uint32_t k = 0; k < (uint32_t)KMAX; ++k)
+        if (k < e_c) at32(a.slot, k * G + g) = l_slot[k][tid];
+    }
+    const uint32_t vals[ST_N + 1] = {st_msgs, st_app, st_vote, st_drop, st_commit, L.won, L.lost, 0,
+                                     (uint32_t)(L.last - last0), L.nev};
+    reduce_stats(a, l_stats, vals);  // (ends with a barrier: l_pf and l_efill are final)
+    // ---- close the partitions k_apply_lead would only hand over (its fast_close)
+    if (tid < NP * FLAG_WORDS) {
+      const uint32_t p = tid / FLAG_WORDS, j = tid % FLAG_WORDS, part = (bk << sl) + w * NP + p;
+      if (part < a.NB && l_ok[p]) a.pflag[(size_t)part * FLAG_WORDS + j] = l_pf[p * FLAG_WORDS + j];
+    }
+    if (tid < NP) {
+      const uint32_t part = (bk << sl) + w * NP + tid;
+      if (part < a.NB) {
+        a.lskip[part] = (uint8_t)l_ok[tid];
+        if (l_ok[tid]) {
+          a.ev_off[2 * part] = (uint64_t)part * PART * a.ev_per_msg;
+          a.ev_counts[2 * part] = 0;
+          a.ev_counts[2 * part + 1] = l_efill[tid];
+          uint32_t any = 0;
+#pragma unroll
+          for (uint32_t j = 0; j < FLAG_WORDS; ++j) any |= l_pf[tid * FLAG_WORDS + j];
+          const uint32_t xs = blockIdx.x & 7;  // (= the bucket's XCD slot, as k_apply_lead's)
+          if (any) a.ap_list[(size_t)xs * a.NB + atomicAdd(&a.ap_cnt[xs * CTR_STRIDE], 1u)] = part;
         }
       }
     }
@@ -1834,9 +1789,6 @@ __global__ void __launch_bounds__(PART, HB_FAST_WAVES) k_apply_fast(ApplyArgs a)
 // loop not unrolled (neutral), the next group's first-round loads issued
 // before this group's second round (+8 %: 128 VGPRs already, it spills).
 // ---------------------------------------------------------------------------
-#ifndef HB_ROUTE_FAST
-#define HB_ROUTE_FAST 1
-#endif
 #ifndef HB_RF_UNROLL
 #define HB_RF_UNROLL 4  // records in flight per lane in the route phase
 #endif
@@ -2325,12 +2277,6 @@ __global__ void __launch_bounds__(PART, HB_GEN_WAVES) k_apply(ApplyArgs a) {
 #ifndef HB_ELECT_GRID  // persistent over the XCD-slot lists (cfg4 -9 to -11 us, cfg3 -3 to -6 us vs one
 #define HB_ELECT_GRID 1024  // workgroup per partition: an empty or short list launched 16K workgroups)
 #endif
-#ifndef HB_ELECT_EAGER
-#define HB_ELECT_EAGER 1
-#endif
-#ifndef HB_ELECT_PF
-#define HB_ELECT_PF 1
-#endif
 constexpr uint32_t ELECT_GRID = HB_ELECT_GRID;
 static_assert(ELECT_GRID % 8 == 0, "k_elect strides its XCD-slot lists by gridDim.x / 8");
 
@@ -2348,9 +2294,9 @@ __global__ void __launch_bounds__(PART, HB_ELECT_WAVES) k_elect(ApplyArgs a) {
   const uint32_t tid = threadIdx.x;
   const uint32_t xs = blockIdx.x & 7, stride = gridDim.x >> 3;
   const uint32_t nl = __hip_atomic_load(&a.el_cnt[xs * CTR_STRIDE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#if HB_ELECT_PF
   // the partition list two ahead and the next partition's flags and event fill
-  // are fetched during this partition's work (two round trips off each turn)
+  // are fetched during this partition's work (two round trips off each turn:
+  // cfg4 1.741-1.762 -> 1.734-1.742 ms)
   const uint32_t* list = a.el_list + (size_t)xs * a.NB;
   uint32_t i = blockIdx.x >> 3;
   uint32_t part = i < nl ? list[i] : 0u;
@@ -2372,18 +2318,6 @@ __global__ void __launch_bounds__(PART, HB_ELECT_WAVES) k_elect(ApplyArgs a) {
     if (tid == 0) l_fill = pfill;  // after k_apply_fast's events
     if (tid <= ST_N) l_stats[tid] = 0;
     __syncthreads();
-#else
-  for (uint32_t i = blockIdx.x >> 3; i < nl; i += stride) {  // uniform
-    const uint32_t part = a.el_list[(size_t)xs * a.NB + i];
-    const uint32_t g = part * PART + tid;
-    if (tid < FLAG_WORDS) {
-      l_flag[tid] = a.pflag[(size_t)part * FLAG_WORDS + tid];
-      l_eflag[tid] = a.eflag[(size_t)part * FLAG_WORDS + tid];
-    }
-    if (tid == 0) l_fill = a.ev_counts[2 * part + 1];  // after k_apply_fast's events
-    if (tid <= ST_N) l_stats[tid] = 0;
-    __syncthreads();
-#endif
     const bool flagged = (l_eflag[tid >> 5] >> (tid & 31)) & 1u;  // (a subset of the k_apply flags)
     ElectLane<NMAX> L;
     L.S = a.S;
@@ -2401,9 +2335,10 @@ __global__ void __launch_bounds__(PART, HB_ELECT_WAVES) k_elect(ApplyArgs a) {
     L.won = L.lost = L.nev = 0;
     L.committed = L.last = 0;
     uint32_t key[KS];  // the slots' arrival keys (0xFFFFFFFF past cnt)
-#if HB_ELECT_EAGER
     // every load of a flagged lane in the round trip of meta / cnt / resume: the
-    // state, commit0 and all KS slots (those past cnt are masked here)
+    // state, commit0 and all KS slots (those past cnt are masked here); loading
+    // only a lane that is `mine`, after that test, measured cfg4 1.813-1.815 vs
+    // 1.763-1.765 ms
     uint64_t c0 = 0;
     if (flagged) {
       L.load();
@@ -2418,8 +2353,6 @@ __global__ void __launch_bounds__(PART, HB_ELECT_WAVES) k_elect(ApplyArgs a) {
         key[k] = r.y;
       }
     }
-#endif
-#if HB_ELECT_PF
     const uint32_t nn = i + 2 * stride < nl ? list[i + 2 * stride] : 0u;
     if (i + stride < nl) {
       if (tid < FLAG_WORDS) {
@@ -2428,23 +2361,9 @@ __global__ void __launch_bounds__(PART, HB_ELECT_WAVES) k_elect(ApplyArgs a) {
       }
       if (tid == 0) pfill = a.ev_counts[2 * nxt + 1];
     }
-#endif
     if (mine) {
-#if !HB_ELECT_EAGER
-      L.load();
-#endif
       last0 = L.last;
-#if HB_ELECT_EAGER
       commit0 = ((resume >> 30) & 1u) ? L.committed : c0;
-#else
-      commit0 = ((resume >> 30) & 1u) ? L.committed : a.commit0[g];
-#pragma unroll
-      for (uint32_t k = 0; k < KS; ++k) {
-        const uint4 r = k < cnt ? at32(a.slot, k * a.S.G + g) : make_uint4(0, 0xFFFFFFFFu, 0, 0);
-        l_slot[k][tid] = r;
-        key[k] = r.y;
-      }
-#endif
       // arrival order of the slots (odd-even transposition, slot numbers as nibbles)
       const uint32_t perm = arrival_perm<KS>(key);
       const uint32_t skip = resume & 0x3FFFFFFFu;
@@ -2490,16 +2409,11 @@ __global__ void __launch_bounds__(PART, HB_ELECT_WAVES) k_elect(ApplyArgs a) {
     if (tid < FLAG_WORDS) a.pflag[(size_t)part * FLAG_WORDS + tid] = l_flag[tid];
     if (tid == 0) a.ev_counts[2 * part + 1] = l_fill;
     __syncthreads();  // the next partition reuses the LDS
-#if HB_ELECT_PF
     part = nxt;
     nxt = nn;
-#endif
   }
 }
 
-#ifndef HB_LEAD_XSTAGE
-#define HB_LEAD_XSTAGE 1
-#endif
 #ifndef HB_LEAD_XWAVES  // k_apply_lead<5> in X mode (LDS: 4 staged slots + the lane rows = 36 KB)
 #define HB_LEAD_XWAVES 4
 #endif
@@ -2518,29 +2432,22 @@ __global__ void __launch_bounds__(PART, HB_ELECT_WAVES) k_elect(ApplyArgs a) {
 // response a leader steps at its own term.  One load and one store of the
 // group's state for the whole batch.  What it cannot take is handed over as
 // k_apply_fast does (resume word, pflag; eflag for k_elect: a group that is no
-// leader, or a leader stopped by a higher-term message).  A leader without a
-// proposal and with more messages than n - 1 (an election storm's leader)
-// first reads only its Term and its slots' terms: with a higher term among
-// them it is handed over unloaded.
+// leader, or a leader stopped by a higher-term message).  Which groups it loads
+// and which it hands over unloaded is handover_class's rule.
 // ---------------------------------------------------------------------------
 // X mode (follower-side batches): a follower whose messages all sit in its
 // first FOLLOW_SLOTS route slots is stepped by FollowLane in the same pass
 // (the follower side of a node with n >= 5 replicas: about (n-1)/n of its
 // groups), the slots' {m.LogTerm, m.Commit} extensions staged beside them.
 constexpr uint32_t FOLLOW_SLOTS = 4;
-// Leaders' Match / Next in LDS (LeadLaneL) or in registers (LeadLane), per n
-#ifndef HB_LEAD_LDS5
-#define HB_LEAD_LDS5 1
-#endif
-#ifndef HB_LEAD_LDS7
-#define HB_LEAD_LDS7 0  // n = 7: 28 KB of {Match, Next} leave 2 workgroups per CU (cfg4 2.018 vs 1.918 ms)
-#endif
+// Leaders' Match / Next in LDS (LeadLaneL, n = 5) or in registers (LeadLane,
+// n = 7: 28 KB of {Match, Next} leave 2 workgroups per CU, cfg4 2.018 vs 1.918 ms)
 template <int NMAX> struct LeadOf {
-  static constexpr bool LDS = NMAX <= 5 ? HB_LEAD_LDS5 : HB_LEAD_LDS7;
+  static constexpr bool LDS = NMAX <= 5;
   using T = typename std::conditional<LDS, LeadLaneL<NMAX>, LeadLane<NMAX>>::type;
 };
 template <int NMAX, bool X>
-__global__ void __launch_bounds__(PART, NMAX <= 5 ? (X && HB_LEAD_XSTAGE ? HB_LEAD_XWAVES : HB_LEAD_WAVES)
+__global__ void __launch_bounds__(PART, NMAX <= 5 ? (X ? HB_LEAD_XWAVES : HB_LEAD_WAVES)
                                                  : HB_LEAD7_WAVES) k_apply_lead(ApplyArgs a) {
   constexpr uint32_t KS = route_kmax(NMAX);
   constexpr uint32_t FS = X ? FOLLOW_SLOTS : 1u;
@@ -2549,12 +2456,11 @@ __global__ void __launch_bounds__(PART, NMAX <= 5 ? (X && HB_LEAD_XSTAGE ? HB_LE
   __shared__ uint32_t l_flag[FLAG_WORDS];
   __shared__ uint32_t l_eflag[FLAG_WORDS];
   __shared__ uint64_t l_stats[ST_N + 1];
-  // the lane's route slots, read once (as in k_elect) — unless the route wrote
-  // them in arrival order (HB_ROUTE_SORTED): then slot x is read for message x.
-  // X mode stages only the first FS (a follower's; a leader reads the rest from
-  // HBM), so that the kernel fits 4 workgroups per CU (HB_LEAD_XSTAGE)
-  constexpr uint32_t SR = HB_ROUTE_SORTED ? 0u : ((X && HB_LEAD_XSTAGE) ? FS : KS);
-  __shared__ uint4 l_slot[SR ? SR : 1][SR ? PART : 1];
+  // the lane's route slots, read once (as in k_elect).  X mode stages only the
+  // first FS (a follower's; a leader reads the rest from HBM), so that the
+  // kernel fits 4 workgroups per CU
+  constexpr uint32_t SR = X ? FS : KS;
+  __shared__ uint4 l_slot[SR][PART];
   // per lane, one 16-byte word per slot: a leader's {Match, Next} (LeadLaneL) or,
   // X mode, a follower's slot extensions {m.LogTerm, m.Commit} — a lane is one or the other
   constexpr uint32_t LW = LDS ? (NMAX > FS ? NMAX : FS) : (X ? FS : 1u);
@@ -2566,8 +2472,7 @@ __global__ void __launch_bounds__(PART, NMAX <= 5 ? (X && HB_LEAD_XSTAGE ? HB_LE
   const uint32_t g = part * PART + tid;
   const bool gvalid = g < a.S.G;
   auto slot_at = [&](uint32_t k) -> uint4 {
-    if constexpr (SR == 0) return at32(a.slot, k * a.S.G + g);
-    else if constexpr (SR < KS) return k < SR ? l_slot[k < SR ? k : 0][threadIdx.x] : at32(a.slot, k * a.S.G + g);
+    if constexpr (SR < KS) return k < SR ? l_slot[k < SR ? k : 0][threadIdx.x] : at32(a.slot, k * a.S.G + g);
     else return l_slot[k][threadIdx.x];
   };
   if (tid == 0) l_fill = l_pfill = 0;
@@ -2591,8 +2496,6 @@ __global__ void __launch_bounds__(PART, NMAX <= 5 ? (X && HB_LEAD_XSTAGE ? HB_LE
   const bool fits = cnt <= KS;  // every message of the group is in its slots
   // r.Commit = 0 (M_NC): the general lane steps the group's first message
   const bool nc = (L.mlo & (uint32_t)M_NC) != 0;
-  // a leader with a proposal or at most one message per follower loads at once
-  const bool spec = leader && !nc && (prop_raw != 0 || (fits && cnt <= (uint32_t)NMAX - 1));
   // X mode: a follower whose messages all sit in its first FS slots, without a
   // dense proposal (stepFollower forwards it: the general lane)
   const bool fol = X && live && !nc && L.state() == HB_STATE_FOLLOWER && cnt > 0 && cnt <= FS && prop_raw == 0;
@@ -2600,41 +2503,32 @@ __global__ void __launch_bounds__(PART, NMAX <= 5 ? (X && HB_LEAD_XSTAGE ? HB_LE
   L.nev = 0;
   // (without X, loading the state beside meta, as k_apply_fast does, measured
   // neutral on cfg3 and +4.5 % on cfg4, whose lanes are mostly not leaders)
-  // (a busy leader with a higher-term message — the route's CNT_HIGHER — is
-  // handed over without reading its slots or its state)
-  const bool busy_hi = leader && !nc && fits && !spec && (craw & CNT_HIGHER) != 0;
-  const bool slots = (leader && !nc && fits && !busy_hi) || fol;
-  if constexpr (SR > 0) {
+  // What to do with the group before its first message is handover_class, the
+  // rule k_route closes partitions by (an election storm's leader is handed
+  // over without reading its slots or its state).  This kernel's own cases,
+  // which the route never closes: a follower of X mode (fol), and a leader
+  // with a dense proposal, which is loaded whatever its messages.
+  const uint32_t cls = handover_class(L.mlo, cnt, (craw & CNT_HIGHER) != 0, (uint32_t)NMAX, KS);
+  const bool loaded = prop_raw != 0 ? (leader && !nc) : cls == HO_LOAD;
+  const bool slots = (loaded && fits) || fol;
 #pragma unroll
-    for (uint32_t k = 0; k < SR; ++k)
-      if (slots && k < cnt) l_slot[k][tid] = at32(a.slot, k * a.S.G + g);
-  }
+  for (uint32_t k = 0; k < SR; ++k)
+    if (slots && k < cnt) l_slot[k][tid] = at32(a.slot, k * a.S.G + g);
   if constexpr (X) {
 #pragma unroll
     for (uint32_t k = 0; k < FS; ++k)
       if (fol && k < cnt) l_lane[k][tid] = at32(a.slotx, k * a.S.G + g);
   }
-  if (spec) L.load(X);
+  if (loaded) L.load(X);
   if (fol) L.load_follow();  // (a follower reads no Progress)
-  bool loaded = spec, higher = busy_hi;
-  if (slots && !spec && !fol) {  // a busy leader without a proposal and no higher term: load it
-    L.load(X);
-    loaded = true;
-  }
-  // the slots' arrival indices, only for a group this kernel steps (an election
-  // storm's leaders go to k_elect without them)
+  // k_elect's, if handed over: no leader, or a leader a higher term steps down
+  bool elect = prop_raw != 0 ? !leader : cls == HO_ELECT;
+  // the slots' arrival indices, only for a group this kernel steps
   uint32_t key[KS];
-  const bool keys = (slots && loaded) || fol;
 #pragma unroll
-  for (uint32_t k = 0; k < KS; ++k) key[k] = (!HB_ROUTE_SORTED && keys && k < cnt) ? slot_at(k).y : 0xFFFFFFFFu;
+  for (uint32_t k = 0; k < KS; ++k) key[k] = (slots && k < cnt) ? slot_at(k).y : 0xFFFFFFFFu;
   // arrival order of the slots (slot numbers as nibbles)
-  uint32_t perm = 0;
-  if (HB_ROUTE_SORTED) {
-#pragma unroll
-    for (uint32_t k = 0; k < KS; ++k) perm |= k << (4 * k);
-  } else {
-    perm = arrival_perm<KS>(key);
-  }
+  const uint32_t perm = arrival_perm<KS>(key);
   const uint64_t last0 = L.last, commit0 = L.committed;
   bool flagged = false;
   uint32_t resume = 0;
@@ -2686,7 +2580,7 @@ __global__ void __launch_bounds__(PART, NMAX <= 5 ? (X && HB_LEAD_XSTAGE ? HB_LE
       resume = 0;
     } else {
       uint32_t x = 0;
-      uint4 nx = slot_at(perm & 0xF);  // (sorted slots: the next one's load runs ahead of this step)
+      uint4 nx = slot_at(perm & 0xF);  // (the next slot's load runs ahead of this step)
 #pragma nounroll
       for (; x < cnt; ++x) {
         if (L.faulted()) break;
@@ -2704,7 +2598,7 @@ __global__ void __launch_bounds__(PART, NMAX <= 5 ? (X && HB_LEAD_XSTAGE ? HB_LE
         if (!L.takes(type, from, mterm)) {
           flagged = true;
           resume = x;
-          higher = mterm > L.term;
+          elect = mterm > L.term;
           break;
         }
         L.arrival = morig;
@@ -2719,8 +2613,7 @@ __global__ void __launch_bounds__(PART, NMAX <= 5 ? (X && HB_LEAD_XSTAGE ? HB_LE
   if (loaded) L.store();
   if (fstepped) L.store_follow();
   const bool stored = loaded || fstepped;
-  // k_elect's candidates (n >= 5): no leader, or a leader a higher term steps down
-  if constexpr (NMAX >= 5) flag_put<true>(l_eflag, tid, flagged && (!leader || higher));
+  if constexpr (NMAX >= 5) flag_put<true>(l_eflag, tid, flagged && elect);  // k_elect's candidates
   flag_put<true>(l_flag, tid, flagged);
   if (flagged) {
     a.resume[g] = resume | (stored ? 0u : 1u << 30);
@@ -2772,9 +2665,6 @@ __global__ void __launch_bounds__(PART, HB_GEN_WAVES) k_follow(ApplyArgs a) {
 // machine.  Events go to the partition's P chunk (at most one
 // step per group, so the chunk's ev_per_msg x PART words bound them).
 // ---------------------------------------------------------------------------
-#ifndef HB_TICK_ELECT
-#define HB_TICK_ELECT 1  // a tick's campaigns through ElectLane (reset form, M_RS)
-#endif
 template <int NMAX>
 __global__ void __launch_bounds__(PART, 2) k_tick(ApplyArgs a) {
   __shared__ uint32_t l_fill;
@@ -2863,8 +2753,7 @@ __global__ void __launch_bounds__(PART, 2) k_tick(ApplyArgs a) {
       L.ev(HB_EV_HEARTBEAT, s, 0, umin64(mt[s], committed));
       if (pmv[s] & PM_PAUSED) a.S.pm[(size_t)s * a.S.G + g] = pmv[s] & ~PM_PAUSED;
     }
-  } else if (type == HB_MSG_HUP && HB_TICK_ELECT && !sz_on(a.S.max_msg_size) && !(L.meta & M_NC) &&
-             L.self() < L.n()) {
+  } else if (type == HB_MSG_HUP && !sz_on(a.S.max_msg_size) && !(L.meta & M_NC) && L.self() < L.n()) {
     // a non-leader's election timeout: campaign through the election lane
     // (hipbatch_elect.h, as k_elect steps it), which leaves the n Progress
     // entries in the reset form (M_RS) instead of writing them — ~4 % of the
@@ -3668,7 +3557,7 @@ struct hb_handle {
   uint32_t* hist = nullptr;       // [tiles][RDX_BINS]
   uint32_t* n_valid = nullptr;    // messages kept after pass 1 (device)
   uint32_t* totals = nullptr;     // [RDX_BINS] digit totals of the current pass
-  // one-pass direct offsets (HB_RDX_DIRECT): hist workgroup sums, rotating superblock sums
+  // one-pass direct offsets: hist workgroup sums, rotating superblock sums
   uint32_t* hagg = nullptr;       // [hist workgroups][RDX_BINS]
   uint32_t* hsup = nullptr;       // [SUP_BUFS][sup_max][RDX_BINS]
   uint32_t sup_max = 0, sup_k = 0;
@@ -3685,7 +3574,7 @@ struct hb_handle {
   bool no_small = false;
   uint32_t kern = 0;  // hb_step_kernels of the last step
   uint32_t fuse = 2;  // k_route_fast: 0 never, 1 one-pass handles, 2 every geometry (HB_ROUTE_FUSE at hb_create)
-  uint32_t storm = 2;  // n >= 5: the route's storm hand-over, 2: with the election lane (HB_STORM=0/1/2 at hb_create)
+  uint32_t storm = 2;  // n >= 5: 2: the route's storm hand-over, 0: off (HB_STORM=0 at hb_create)
   uint32_t agrid = 0;  // the apply kernels' grid (apply_grid_for)
   uint32_t bk_bits = 1;            // bits of a bucket id
   // host-pointer staging
@@ -3857,7 +3746,7 @@ uint32_t route_grid(const hb_handle* h, bool x) {
 template <int KMAX>
 void launch_route(hb_handle* h, const ApplyArgs& a, hipStream_t st) {
   if constexpr (KMAX >= 5) {
-    if (!a.slotx && a.storm >= 2) {  // the storm hand-over with the election lane in the route
+    if (a.storm) {  // the storm hand-over (never an X step's: hb_step)
       if (h->nmax <= 5)
         hipLaunchKernelGGL((k_route<KMAX, false, 5>), dim3(route_grid<KMAX>(h, false)), dim3(ROUTE_THREADS), 0, st, a);
       else
@@ -3979,7 +3868,7 @@ int hb_create(int device, uint32_t capacity, uint32_t max_replicas, uint32_t max
   h->NB = (capacity + PART - 1) / PART;
   if (const char* e = getenv("HB_SMALL_STEP")) h->no_small = e[0] == '0';
   if (const char* e = getenv("HB_ROUTE_FUSE")) h->fuse = (uint32_t)atoi(e);
-  if (const char* e = getenv("HB_STORM")) h->storm = (uint32_t)atoi(e);
+  if (const char* e = getenv("HB_STORM")) h->storm = atoi(e) == 0 ? 0u : 2u;
   const size_t G = capacity, R = h->nmax;
   DevState& s = h->st;
   s.G = capacity;
@@ -4874,7 +4763,7 @@ int hb_step(hb_handle* h, const hb_batch* b, uint32_t flags) {
       const uint32_t dm = h->passes > 1;  // digit-major tile counts (k_scan_rows)
       const uint32_t nhw = (ntiles + HIST_TPB - 1) / HIST_TPB;
       const dim3 sg((ntiles + SCAT_TPW - 1) / SCAT_TPW);
-      if (HB_RDX_DIRECT && h->passes == 1) {  // hist + direct scatter: no scan launch
+      if (h->passes == 1) {  // hist + direct scatter: no scan launch
         const uint32_t k = h->sup_k, kn = (k + 1) % SUP_BUFS;
         const size_t bw = (size_t)h->sup_max * RDX_BINS;
         DirectSums dsum{h->hagg, h->hsup + k * bw, h->hsup + kn * bw, h->sup_used[kn] * RDX_BINS,
@@ -4966,11 +4855,11 @@ int hb_step(hb_handle* h, const hb_batch* b, uint32_t flags) {
   aa.lskip = h->lskip;
   // the route's storm hand-over writes the handle's flags and lists: only when
   // the apply of the previous step is not running beside it (one stream)
-  aa.storm = (HB_ROUTE_STORM && h->nmax >= 5 && !two && !xmode && !bd.props) ? h->storm : 0u;
+  aa.storm = (h->nmax >= 5 && !two && !xmode && !bd.props) ? h->storm : 0u;
   // n = 3, prep and apply on one stream: the route runs inside the fast
   // kernel's workgroups (k_route_fast; two-pass handles too: cfg5 0.998 ->
   // 0.931 ms/step same box)
-  const bool fused = HB_ROUTE_FAST && h->nmax == 3 && !two && (h->fuse >= 2 || (h->fuse == 1 && h->passes == 1)) &&
+  const bool fused = h->nmax == 3 && !two && (h->fuse >= 2 || (h->fuse == 1 && h->passes == 1)) &&
                      PART_LOG + h->sis_log >= route_fast_rg_log(aa.kmax, xmode);
   switch (h->nmax) {
     case 3:
@@ -5003,7 +4892,7 @@ int hb_step(hb_handle* h, const hb_batch* b, uint32_t flags) {
     h->prof_n++;
   }
   h->stepped = true;
-  h->kern = (fused ? HB_KERN_ROUTE_FAST : 0u) | (aa.storm >= 2 ? HB_KERN_ROUTE_ELECT : 0u);
+  h->kern = (fused ? HB_KERN_ROUTE_FAST : 0u) | (aa.storm ? HB_KERN_ROUTE_ELECT : 0u);
   return HB_OK;
 }
 

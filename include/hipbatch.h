@@ -607,8 +607,7 @@ int  hb_phase_reset(hb_handle* h);
  * k_apply_fast / k_apply_lead separately.  HB_KERN_ROUTE_ELECT = (n >= 5,
  * batches without dense proposals) the route closed the partitions whose
  * groups k_apply_lead would only hand over and ran the election lane there
- * (k_route<8, false, n>; HB_STORM=0/1 at hb_create turns it off / keeps only
- * the hand-over). */
+ * (k_route<8, false, n>; HB_STORM=0 at hb_create turns it off). */
 #define HB_KERN_ROUTE_FAST 1u
 #define HB_KERN_ROUTE_ELECT 2u
 int  hb_step_kernels(hb_handle* h, uint32_t* mask);

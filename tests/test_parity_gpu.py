@@ -176,14 +176,25 @@ def test_pipelined_steps_with_input_stream():
     assert_groups_equal(eng.get_groups(), og.groups(), "pipelined")
 
 
+def _storm_env(monkeypatch, storm):
+    """HB_STORM as hb_create reads it: unset (the hand-over on, the default) or "0" (off)."""
+    if storm is None:
+        monkeypatch.delenv("HB_STORM", raising=False)
+    else:
+        monkeypatch.setenv("HB_STORM", storm)
+
+
+@pytest.mark.parametrize("storm", [None, "0"])
 @pytest.mark.parametrize("n", [5, 7])
-def test_cfg4_storm_repeatable_stream(n):
+def test_cfg4_storm_repeatable_stream(n, storm, monkeypatch):
     """The bench's repeatable cfg4 storm: step-down, campaign, n-1 votes, replayed
     at +4 terms per step on the state the previous storm left.  Every partition
     holds only groups k_apply_lead would hand over unloaded, so the route closes
     them (storm hand-over, k_route); the last step adds one leader to step in
     partition 3 (a MsgHeartbeatResp at its own term), so k_apply_lead runs that
-    partition and the route closes the others."""
+    partition and the route closes the others.  With HB_STORM=0 the same stream
+    goes through k_route + k_apply_lead + k_elect."""
+    _storm_env(monkeypatch, storm)
     G = 2500
     g, runs = synth.election_groups(G, n, seed=21)
     pair = Pair(g, runs, n, 64, max_batch=8 * G)
@@ -191,7 +202,8 @@ def test_cfg4_storm_repeatable_stream(n):
     for k in range(3):
         _, st, _ = pair.step(dict(b, term=synth.storm_terms(b["term"], k)), ctx=f"storm {k}")
         assert st[abi.HB_STAT_VOTERESP] == G * (n - 1) and st[abi.HB_STAT_WON] > 0
-        assert pair.eng.step_kernels() & abi.HB_KERN_ROUTE_ELECT  # (the election lane ran in the route)
+        # (the election lane ran in the route)
+        assert bool(pair.eng.step_kernels() & abi.HB_KERN_ROUTE_ELECT) == (storm is None)
     now = pair.og.groups()
     lead = np.flatnonzero((now["state"] == abi.HB_STATE_LEADER) & (np.arange(G) // 256 == 3))
     assert len(lead)
@@ -204,6 +216,81 @@ def test_cfg4_storm_repeatable_stream(n):
     b3["term"] = np.append(b3["term"], np.uint64(now["term"][x]))
     b3["index"] = np.append(b3["index"], np.uint64(0))
     pair.step(b3, ctx="storm 3 + a leader")
+
+
+def _handover_class(x):
+    """The class of group x in test_storm_handover_class_boundaries."""
+    p, j = divmod(x, 256)
+    if j == 255:
+        return "removed"
+    if j == 254 and p >= 1:
+        return ("over", "step")[p - 1]
+    if j == 253 and p == 2:
+        return "busy"
+    return ("hup", "nc", "n_hi", "ks_hi")[j % 4]
+
+
+@pytest.mark.parametrize("storm", [None, "0"])
+@pytest.mark.parametrize("n", [5, 7])
+def test_storm_handover_class_boundaries(n, storm, monkeypatch):
+    """The edges of the storm hand-over rule (handover_class: what k_apply_lead
+    does with a group before its first message, and so which partitions k_route
+    closes), three partitions of 256 groups, every group with messages, no
+    proposals.  Every partition holds followers with a MsgHup and n - 1 votes
+    (after a step-down, so that the second step is a fresh election), leaders with r.Commit unknown, leaders with exactly n and exactly route_kmax
+    (8) messages one of which carries Term + 1, and a removed group that still
+    receives a message: all handed over unloaded, so partition 0 is closed by
+    the route.  Partition 1 adds a leader with route_kmax + 1 messages (more
+    than its slots: the partition stays open); partition 2 adds a leader with
+    n - 1 messages at its own term (stepped in place) and one with n messages
+    and no higher term (loaded).  Two steps, the second at +4 terms on the
+    state the first left; with HB_STORM=0 k_apply_lead runs every partition."""
+    _storm_env(monkeypatch, storm)
+    G, ks = 768, 8
+    lead, lruns = synth.steady_groups(G, n, seed=171, last_hi=1 << 12)
+    g, runs = synth.election_groups(G, n, seed=172)
+    cls = [_handover_class(x) for x in range(G)]
+    for x in range(G):
+        if cls[x] != "hup":
+            g[x], runs[x] = lead[x], lruns[x]
+        if cls[x] == "nc":
+            g[x]["commit_zero"] = 1
+    hb = abi.HB_MSG_HEARTBEAT_RESP
+    rows = []  # (group, its k-th message, info, term)
+    for x in range(G):
+        t = int(g["term"][x])
+        if cls[x] == "hup":  # as synth.cfg4_storm_batch: down to Term + 1, campaign at Term + 2, the votes
+            rows += [(x, 0, hb | (1 << 4), t + 1), (x, 1, abi.HB_MSG_HUP, 0)]
+            for s in range(1, n):  # (a third of the votes reject; every third candidate loses)
+                rej = (x // 4 + s) % 3 == 0 or x % 12 == 0
+                rows.append((x, 1 + s, abi.HB_MSG_VOTE_RESP | (s << 4) | (rej << 8), t + 2))
+            continue
+        c = {"removed": 1, "nc": 2, "n_hi": n, "ks_hi": ks, "over": ks + 1, "step": n - 1, "busy": n}[cls[x]]
+        hi = (x // 4) % c if cls[x] in ("n_hi", "ks_hi", "over") else -1  # which message carries Term + 1
+        rows += [(x, k, hb | ((1 + k % (n - 1)) << 4), t + (k == hi)) for k in range(c)]
+    rows = np.array(rows, dtype=np.uint64)
+    # arrival order: every group's k-th message before any (k + 1)-th, groups shuffled within a round
+    order = np.lexsort((np.random.default_rng(173).random(len(rows)), rows[:, 1]))
+    rows = rows[order]
+    b = dict(group=rows[:, 0].astype(np.uint32), info=rows[:, 2].astype(np.uint32), term=rows[:, 3].copy(),
+             index=np.zeros(len(rows), np.uint64), hint=None, props=None)
+    pair = Pair(g, runs, n, 8, max_batch=1 << 13)
+    removed = np.array([x for x in range(G) if cls[x] == "removed"])
+    for x in removed:
+        pair.eng.remove_groups(int(x), 1)
+        pair.og.raft(int(x)).n = 0
+    dev_groups = pair.eng.get_groups
+
+    def groups_but_removed():  # (a removed group's record is unspecified beyond n = 0)
+        d = dev_groups()
+        assert (d["n"][removed] == 0).all()
+        d[removed] = pair.og.groups()[removed]
+        return d
+    pair.eng.get_groups = groups_but_removed
+    for k in range(2):
+        _, st, _ = pair.step(dict(b, term=synth.storm_terms(b["term"], k)), ctx=f"hand-over classes {k}")
+        assert bool(pair.eng.step_kernels() & abi.HB_KERN_ROUTE_ELECT) == (storm is None)
+        assert st[abi.HB_STAT_WON] > 0 and st[abi.HB_STAT_LOST] > 0
 
 
 @pytest.mark.parametrize("W", [8, 256])

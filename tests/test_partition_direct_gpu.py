@@ -1,4 +1,4 @@
-"""Partitions with direct tile offsets (HB_RDX_DIRECT, r06): the
+"""Partitions with direct tile offsets (one-pass handles, r06): the
 histogram kernel's workgroup and superblock digit sums stand in for the
 k_scan_rows launch, and the scatter sums them before each tile.  These steps
 pin what the full-size headline tests do not reach: batch sizes that change
