@@ -17,12 +17,35 @@ from .test_multinode_gpu import _dev_msgs, _orc_msgs
 G, ROUNDS, CAPACITY = 96, 60, 128
 
 
-def run_random_scenario(seed, n, setup=None, after_advance=None):
+def _bootstrap(mn, gid, peers, draws):
+    """CreateGroup with peers, and the oracle raft in the same state: the
+    bootstrap of raft/multinode.go:197-211 (becomeFollower(1, None), one entry
+    per peer at term 1, committed = len(peers)) with r.Commit (HardState.Commit)
+    still 0 until the group's first Step (raft/raft.go:488).  Returns the
+    storage, the oracle, the HardState the node starts from and the lowest
+    index a response may name (0)."""
+    from oracle.pyoracle import Raft
+    n = len(peers)
+    s = MemoryStorage()
+    mn.CreateGroup(gid, Config(election=3, heartbeat=1), s, peers=peers)
+    o = Raft(1, peers, ents=[(i, 1) for i in range(1, n + 1)], max_inflight=8,
+             election=3, heartbeat=1, draws=draws)
+    o.r.Term = 1
+    o.r.log.committed = n
+    assert o.Commit == 0
+    return s, o, (1, 0, 0), 0
+
+
+def run_random_scenario(seed, n, setup=None, after_advance=None, start=_bootstrap):
     """setup(mn): called on the fresh node before any group exists.
+    start(mn, gid, peers, draws): creates group gid on the node and its oracle
+    raft; returns (storage, oracle, the (Term, Vote, Commit) the node starts
+    from, floor): responses name indices in [floor, lastIndex] and proposals'
+    payloads lie above floor + n (_bootstrap: floor 0, a fresh group).
     after_advance(mn, st, gids, rnd): called after every Advance; st[gid]["o"] is
     the group's oracle raft, st[gid].get("dead") says its oracle faulted.
     Returns (mn, st, gids, seen)."""
-    from oracle.pyoracle import Msg, Raft
+    from oracle.pyoracle import Msg
     rng = np.random.default_rng(seed)
     seen = dict(app_ents=0, leaders=0, commits=0, votes=0, beats=0)
     peers = list(range(1, n + 1))
@@ -34,14 +57,11 @@ def run_random_scenario(seed, n, setup=None, after_advance=None):
     gids = [1000 + 17 * g for g in range(G)]
     st = {}
     for gid in gids:
-        s = MemoryStorage()
-        mn.CreateGroup(gid, Config(election=3, heartbeat=1), s, peers=peers)
-        o = Raft(1, peers, ents=[(i, 1) for i in range(1, n + 1)], max_inflight=8,
-                 election=3, heartbeat=1, draws=draws)
-        o.r.Term = 1
-        o.r.log.committed = n
-        assert o.Commit == 0
-        st[gid] = dict(s=s, o=o, data={}, applied=0, prev_hard=(1, 0, 0), prev_soft=(0, 0), seq=0)
+        s, o, hard0, floor = start(mn, gid, peers, draws)
+        st[gid] = dict(s=s, o=o, data={}, applied=0, prev_hard=hard0, prev_soft=(0, 0), seq=0, floor=floor)
+        if s.LastIndex() >= s.FirstIndex():  # a restarted group: the payloads its storage already holds
+            st[gid]["data"] = {e.Index: e.Data for e in s.Entries(s.FirstIndex(), s.LastIndex() + 1)[0]
+                               if e.Data is not None}
     for rnd in range(ROUNDS):
         for gid in gids:
             d, o = st[gid], st[gid]["o"]
@@ -70,8 +90,9 @@ def run_random_scenario(seed, n, setup=None, after_advance=None):
                         o.Step(Msg(abi.HB_MSG_VOTE_RESP, From=frm, Term=term, Reject=rej))
                 elif a < 0.80:
                     rej = bool(rng.random() < 0.15)
-                    idx = int(rng.integers(0, o.lastIndex + 1))
-                    hint = int(rng.integers(0, o.lastIndex + 1))
+                    lo = d["floor"]  # (0 for a fresh group: the draws are those of [0, lastIndex])
+                    idx = lo + int(rng.integers(0, o.lastIndex - lo + 1))
+                    hint = lo + int(rng.integers(0, o.lastIndex - lo + 1))
                     mn.Step(gid, Message(Type=abi.HB_MSG_APP_RESP, From=frm, Term=o.Term, Index=idx, Reject=rej,
                                          RejectHint=hint))
                     if member:
@@ -150,7 +171,8 @@ def run_random_scenario(seed, n, setup=None, after_advance=None):
     # every accepted proposal's payload reached storage in proposal order
     for gid in gids:
         s = st[gid]["s"]
-        ents, err = s.Entries(n + 1, s.LastIndex() + 1) if s.LastIndex() > n else ([], None)
+        lo = st[gid]["floor"] + n + 1
+        ents, err = s.Entries(lo, s.LastIndex() + 1) if s.LastIndex() >= lo else ([], None)
         got = [e.Data for e in (ents or []) if e.Data is not None]
         props = st[gid].get("props", [])
         it = iter(props)

@@ -59,6 +59,7 @@ def assert_inflights_equal(eng, og, groups_now, ctx=""):
 
 class Pair:
     """An engine and an oracle loaded with the same groups."""
+    gpu = True
 
     def __init__(self, groups, runs, nmax, W, ins=None, max_msg_size=abi.HB_NO_LIMIT, max_batch=1 << 16,
                  sizes=None, term_runs=None, oracle_shards=1):
@@ -159,3 +160,71 @@ class Pair:
         if getattr(self, "draws", None) is not None:  # transitions zero r.elapsed
             assert np.array_equal(self.eng.get_timers(), self.og.timers()), f"{ctx}: timers differ"
         return dev_ev, dev_st, ora_g
+
+
+class _NoEngine:
+    """What a scenario asks of Pair.eng beyond stepping, answered by the oracle."""
+
+    def __init__(self, og):
+        self.get_groups = og.groups
+
+    def remove_groups(self, first, count):
+        pass
+
+
+class OraclePair:
+    """Pair's interface over the oracle alone (no GPU): runs a scenario body and
+    records what tests/test_lift.py asserts about it — per batch the share of
+    messages that make REC_LONG records, the event values on either side of
+    2^40, and the faulted groups at the end."""
+    gpu = False
+
+    def __init__(self, groups, runs, nmax, W, ins=None, max_msg_size=abi.HB_NO_LIMIT, max_batch=1 << 16,
+                 sizes=None, term_runs=None, oracle_shards=1):
+        self.og = OracleGroups(groups, runs, W, max_msg_size, ins)
+        self.eng = _NoEngine(self.og)
+        if sizes:
+            self.og.load_sizes(sizes)
+        if term_runs:
+            if term_runs is True:
+                from etcd_amd import synth
+                term_runs = synth.older_runs(self.og.groups(), runs)
+            self.og.load_term_runs(term_runs)
+        self.draws = None
+        self.long_share = []  # per non-empty batch: REC_LONG records / records
+        self.all_long = []    # per non-empty batch: every record with a Term or an Index is long
+        self.ev_wide = self.ev_narrow = 0  # events with x >= 2^40 / below
+        self.commit_wide = self.commit_narrow = 0  # the HB_EV_COMMIT ones among them
+
+    def _count(self, ev):
+        wide = (ev["x"] >> np.uint64(40)) != 0
+        com = ev["type"] == abi.HB_EV_COMMIT
+        self.ev_wide += int(wide.sum())
+        self.ev_narrow += int((~wide).sum())
+        self.commit_wide += int((wide & com).sum())
+        self.commit_narrow += int((~wide & com).sum())
+
+    def set_timers(self, timers, draws):
+        self.draws = np.ascontiguousarray(draws, dtype=np.uint64)
+        self.og.load_timers(timers)
+
+    def tick(self, ctx="", check_inflights=False):
+        ev, st = self.og.tick(self.draws)
+        self._count(ev)
+        return ev, st, self.og.groups()
+
+    def step(self, batch, ctx="", check_inflights=True):
+        if len(batch["group"]):
+            from .lift_util import long_records
+            lng = long_records(batch)
+            # (a MsgProp's index field counts its entries: no log index, Term 0)
+            prop = (np.asarray(batch["info"]) & 0xF) == abi.HB_MSG_PROP
+            valued = ((np.asarray(batch["index"]) != 0) & ~prop) | (np.asarray(batch["term"]) != 0)
+            self.long_share.append(float(lng.mean()))
+            self.all_long.append(bool(lng[valued].all()))
+        ev, st = self.og.step(batch)
+        self._count(ev)
+        return ev, st, self.og.groups()
+
+    def faulted_share(self):
+        return float((self.og.groups()["fault"] != 0).mean())

@@ -14,6 +14,7 @@ from etcd_amd import abi, synth
 from oracle.pyoracle import OracleGroups
 
 from . import wire_util as WU
+from .lift_util import lifted
 from .move_util import MovedPair
 from .test_wire_gpu import _decode_dev
 
@@ -149,6 +150,9 @@ def _case(name):
     if name == "n5_fuzz":
         g, runs, ins = synth.random_groups(G, 5, seed=12, W=W8)
         return g, runs, 5, dict(ins=ins), lambda k, now, rng: synth.random_batch(g, 1200, seed=120 + k)
+    if name == "n5_fuzz_W40":  # the same at the record and event-word boundary (tests/lift_util.py)
+        g, runs, ins = lifted("W40", *synth.random_groups(G, 5, seed=12, W=W8), delta=24, eps=20)
+        return g, runs, 5, dict(ins=ins), lambda k, now, rng: synth.random_batch(g, 1200, seed=120 + k)
     if name == "sized":
         g, runs, ins = synth.random_groups(G, 3, seed=13, W=W8)
         sizes = synth.window_sizes(g, runs, seed=14)
@@ -160,7 +164,7 @@ def _case(name):
     raise KeyError(name)
 
 
-@pytest.mark.parametrize("name", ["n3_lagging", "n5_fuzz", "sized", "mixed_term_runs"])
+@pytest.mark.parametrize("name", ["n3_lagging", "n5_fuzz", "sized", "mixed_term_runs", "n5_fuzz_W40"])
 def test_steps_after_moves_match_oracle(name):
     """300 groups in capacity 320, W = 8: n = 3 leaders with lagging followers
     (cfg3 open loop), n = 5 fuzz with inflight windows, n = 3 with

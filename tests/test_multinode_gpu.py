@@ -99,6 +99,86 @@ def test_multinode_restart_from_snapshot():  # :334-370
     assert rd.Messages == [Message(Type=abi.HB_MSG_VOTE, To=2, From=1, Term=2, LogTerm=1, Index=3)]
 
 
+def test_multinode_restart_from_snapshot_at_a_large_index():
+    """The same restart with the snapshot at Index 2^40 + 5, Term 2^24 + 3: every
+    device event of the group carries an x >= 2^40 (a continuation word, which
+    the host replay of libhbnode expands) and every message it is stepped with
+    is a long record.  A full leader cycle: first Ready, Campaign, a granting
+    MsgVoteResp, Propose, an accepting MsgAppResp.  Every Ready is compared
+    with an oracle raft restarted from the same storage, and with the values
+    the reference gives by hand:
+      campaign          raft/raft.go:396-419: Term + 1, MsgVote{Term, Index: lastIndex, LogTerm: lastTerm}
+      becomeLeader      :357-379: the noop entry at lastIndex + 1 with the new Term
+      bcastAppend       :239-283: MsgApp{Index: Next - 1, LogTerm: term(Next - 1), Commit: committed}
+      MsgAppResp        :520-545: maybeUpdate, maybeCommit (the quorum of 3 is 2), bcastAppend"""
+    from oracle.pyoracle import Msg, Raft
+    S, T = (1 << 40) + 5, (1 << 24) + 3
+    snap = Snapshot(Index=S, Term=T, Nodes=[1, 2, 3])
+    entries = [Entry(Term=T, Index=S + 1, Data=b"foo")]
+    s = MemoryStorage()
+    s.SetHardState(HardState(Term=T, Commit=S + 1))
+    s.ApplySnapshot(snap)
+    s.Append(entries)
+    o = Raft(1, [1, 2, 3], ents=[(S + 1, T)], snapshot=(S, T), hard=(T, 0, S + 1))
+    assert (o.firstIndex, o.lastIndex, o.committed, o.Term) == (S + 1, S + 1, S + 1, T)
+    mn = StartMultiNode(1)
+    mn.CreateGroup(1, Config(10, 1), s)
+    gs = mn.Ready()
+    assert gs[1] == Ready(HardState=emptyState, CommittedEntries=entries)  # the small test's, translated
+    mn.Advance(gs)
+    assert mn.Ready() == {}
+
+    def cycle(ctx):
+        """One Ready / Advance; messages and entries equal the oracle's."""
+        rd = mn.Ready()[1]
+        assert rd.fault == 0 and o.fault == 0, ctx
+        om = _orc_msgs(o)
+        assert _dev_msgs(rd) == om, f"{ctx}: messages\n dev {_dev_msgs(rd)}\n ora {om}"
+        assert [(e.Index, e.Term) for e in rd.Entries] == \
+               [(i, o.term(i)) for i in range(s.LastIndex() + 1, o.lastIndex + 1)], ctx
+        s.Append(rd.Entries)
+        mn.Advance({1: rd})
+        return rd
+
+    mn.Campaign(1)
+    o.Step(Msg(abi.HB_MSG_HUP))
+    rd = cycle("campaign")
+    assert rd.SoftState == SoftState(0, abi.HB_STATE_CANDIDATE) == SoftState(o.lead, o.state)
+    assert rd.HardState == HardState(Term=T + 1, Vote=1, Commit=S + 1) == HardState(o.Term, o.Vote, o.Commit)
+    assert rd.Messages == [Message(Type=abi.HB_MSG_VOTE, To=to, From=1, Term=T + 1, LogTerm=T, Index=S + 1)
+                           for to in (2, 3)]
+
+    mn.Step(1, Message(Type=abi.HB_MSG_VOTE_RESP, From=2, To=1, Term=T + 1))
+    o.Step(Msg(abi.HB_MSG_VOTE_RESP, From=2, Term=T + 1))
+    rd = cycle("vote")
+    noop = Entry(Term=T + 1, Index=S + 2)
+    assert rd.SoftState == SoftState(1, StateLeader) == SoftState(o.lead, o.state)
+    assert rd.HardState == emptyState and (o.Term, o.Vote, o.Commit) == (T + 1, 1, S + 1)
+    assert rd.Entries == [noop] and rd.CommittedEntries == []
+    assert rd.Messages == [Message(Type=abi.HB_MSG_APP, To=to, From=1, Term=T + 1, LogTerm=T, Index=S + 1,
+                                   Commit=S + 1, Entries=[noop]) for to in (2, 3)]
+
+    mn.Propose(1, b"bar")
+    o.Step(Msg(abi.HB_MSG_PROP, From=1, Entries=1))
+    rd = cycle("propose")
+    bar = Entry(Term=T + 1, Index=S + 3, Data=b"bar")
+    assert rd.Entries == [bar] and rd.CommittedEntries == [] and rd.HardState == emptyState
+    assert rd.Messages == []  # both followers are Probe and paused since the noop's MsgApp
+
+    mn.Step(1, Message(Type=abi.HB_MSG_APP_RESP, From=2, To=1, Term=T + 1, Index=S + 3))
+    o.Step(Msg(abi.HB_MSG_APP_RESP, From=2, Term=T + 1, Index=S + 3))
+    rd = cycle("ack")
+    assert rd.CommittedEntries == [noop, bar] and rd.Entries == []
+    assert rd.HardState == HardState(Term=T + 1, Vote=1, Commit=S + 3) == HardState(o.Term, o.Vote, o.Commit)
+    # follower 2 is Replicate at Next S + 4: an empty MsgApp carries the commit; 3 stays paused
+    assert rd.Messages == [Message(Type=abi.HB_MSG_APP, To=2, From=1, Term=T + 1, LogTerm=T + 1, Index=S + 3,
+                                   Commit=S + 3)]
+    st = mn.Status(1)
+    assert st.Progress[2].match == S + 3 and st.Progress[2].next == S + 4 and st.Progress[3].match == 0
+    assert st.Progress[3].next == S + 2 == o.pr(3).Next
+    mn.Stop()
+
+
 def test_multinode_advance():  # :372-394
     storage = MemoryStorage()
     mn = StartMultiNode(1)
@@ -342,6 +422,38 @@ def test_random_multinode_vs_oracle(seed, n):
         props = st[gid].get("props", [])
         it = iter(props)
         assert all(any(p == g for p in it) for g in got), f"group {gid}: payload order"
+
+
+def test_random_multinode_vs_oracle_restarted_at_a_large_index():
+    """The randomised scenario (tests/multinode_scenario.py, the same rounds and
+    the same per-Ready assertions) over groups restarted from a snapshot: the
+    k-th group's snapshot lies at Index 2^40 - 48 + k (the 96 groups straddle
+    2^40 and their logs grow across it), Term 2^24 - 2 (the first campaigns
+    cross 2^24), one entry above it, committed.  Responses name indices from
+    n below the snapshot up (rejections with a hint below firstIndex make the
+    leader send the storage's snapshot).  The host replay of libhbnode expands
+    one-word and two-word device events side by side."""
+    from oracle.pyoracle import Raft
+    from .multinode_scenario import run_random_scenario
+    n, T = 3, (1 << 24) - 2
+    made = []
+
+    def start(mn, gid, peers, draws):
+        S = (1 << 40) - 48 + len(made)
+        made.append(S)
+        s = MemoryStorage()
+        s.SetHardState(HardState(Term=T, Commit=S + 1))
+        s.ApplySnapshot(Snapshot(Index=S, Term=T, Nodes=peers))
+        s.Append([Entry(Term=T, Index=S + 1, Data=b"foo")])
+        mn.CreateGroup(gid, Config(election=3, heartbeat=1), s)
+        o = Raft(1, peers, ents=[(S + 1, T)], snapshot=(S, T), hard=(T, 0, S + 1), max_inflight=8,
+                 election=3, heartbeat=1, draws=draws)
+        return s, o, (T, 0, S + 1), S + 1 - n
+
+    mn, st, gids, seen = run_random_scenario(5, n, start=start)
+    last = [st[g]["o"].lastIndex for g in gids]
+    assert min(last) < 1 << 40 <= max(last) and max(st[g]["o"].Term for g in gids) >= 1 << 24
+    mn.Stop()
 
 
 # ---------------------------------------------------------------- storage compaction / snapshots

@@ -9,6 +9,7 @@ import pytest
 
 from etcd_amd import abi, synth
 
+from .lift_util import lifted
 from .parity_util import Pair
 
 pytestmark = pytest.mark.gpu
@@ -21,9 +22,14 @@ def _empty(G, props=None):
 
 @pytest.mark.parametrize("G,n", [(1, 3), (1000, 3), (3000, 3), (2500, 5), (1500, 7)])
 def test_cfg2_steady_replication(G, n):
+    run_cfg2_steady_replication(G, n)
+
+
+def run_cfg2_steady_replication(G, n, lift=None, make=Pair):
     """cfg2 shape: props + every follower acks; exactly one commit advance per group."""
     g, runs = synth.steady_groups(G, n, seed=11 + G, last_hi=1 << 20)
-    pair = Pair(g, runs, n, 256, max_batch=G * n + 16)
+    g, runs, _ = lifted(lift, g, runs, delta=1 << 19, eps=500)
+    pair = make(g, runs, n, 256, max_batch=G * n + 16)
     for step in range(3):
         _, st, _ = pair.step(synth.cfg2_batch(g, step, seed=5 + step), ctx=f"cfg2 step {step}")
         assert st[abi.HB_STAT_COMMITS] == G
@@ -32,11 +38,16 @@ def test_cfg2_steady_replication(G, n):
 
 @pytest.mark.parametrize("seed,nmax,W", [(1, 3, 8), (2, 5, 8), (3, 7, 4), (4, 3, 256), (5, 7, 16)])
 def test_fuzz_all_message_types(seed, nmax, W):
+    run_fuzz_all_message_types(seed, nmax, W)
+
+
+def run_fuzz_all_message_types(seed, nmax, W, lift=None, make=Pair):
     """Random states (all roles, progress states, inflight windows incl. full)
     and random messages of every device type, incl. stale/higher terms,
     non-members and reference panics."""
     g, runs, ins = synth.random_groups(1800, nmax, seed=seed, W=W)
-    pair = Pair(g, runs, nmax, W, ins=ins, max_batch=1 << 15)
+    g, runs, ins = lifted(lift, g, runs, ins, delta=24, eps=20)
+    pair = make(g, runs, nmax, W, ins=ins, max_batch=1 << 15)
     for k in range(4):
         pair.step(synth.random_batch(g, 6000, seed=100 * seed + k), ctx=f"fuzz {seed}/{k}")
 
@@ -59,12 +70,17 @@ def test_cfg4_election_storm():
 
 
 def test_cfg3_lagging_followers_closed_loop():
+    run_cfg3_lagging_followers_closed_loop()
+
+
+def run_cfg3_lagging_followers_closed_loop(lift=None, make=Pair):
     """Lagging followers, rejects with hints, heartbeats, unreachable, W=8
     (forces the full-inflights pause path); batches are produced by a follower
     simulator from the leader's own MsgApp events."""
     G = 2000
     g, runs = synth.lagging_groups(G, 5, seed=0x5EED0003)
-    pair = Pair(g, runs, 5, 8, max_batch=1 << 16)
+    g, runs, _ = lifted(lift, g, runs, delta=2048, eps=50)
+    pair = make(g, runs, 5, 8, max_batch=1 << 16)
     sim = synth.FollowerSim(g, seed=3)
     b = _empty(G, props=np.ones(G, np.uint32))
     for k in range(6):
@@ -187,6 +203,10 @@ def _storm_env(monkeypatch, storm):
 @pytest.mark.parametrize("storm", [None, "0"])
 @pytest.mark.parametrize("n", [5, 7])
 def test_cfg4_storm_repeatable_stream(n, storm, monkeypatch):
+    run_cfg4_storm_repeatable_stream(n, storm, monkeypatch)
+
+
+def run_cfg4_storm_repeatable_stream(n, storm, monkeypatch, lift=None, make=Pair):
     """The bench's repeatable cfg4 storm: step-down, campaign, n-1 votes, replayed
     at +4 terms per step on the state the previous storm left.  Every partition
     holds only groups k_apply_lead would hand over unloaded, so the route closes
@@ -197,13 +217,14 @@ def test_cfg4_storm_repeatable_stream(n, storm, monkeypatch):
     _storm_env(monkeypatch, storm)
     G = 2500
     g, runs = synth.election_groups(G, n, seed=21)
-    pair = Pair(g, runs, n, 64, max_batch=8 * G)
+    g, runs, _ = lifted(lift, g, runs, delta=1 << 15, eps=500)
+    pair = make(g, runs, n, 64, max_batch=8 * G)
     b = synth.cfg4_storm_batch(g, seed=22)
     for k in range(3):
         _, st, _ = pair.step(dict(b, term=synth.storm_terms(b["term"], k)), ctx=f"storm {k}")
         assert st[abi.HB_STAT_VOTERESP] == G * (n - 1) and st[abi.HB_STAT_WON] > 0
         # (the election lane ran in the route)
-        assert bool(pair.eng.step_kernels() & abi.HB_KERN_ROUTE_ELECT) == (storm is None)
+        assert not pair.gpu or bool(pair.eng.step_kernels() & abi.HB_KERN_ROUTE_ELECT) == (storm is None)
     now = pair.og.groups()
     lead = np.flatnonzero((now["state"] == abi.HB_STATE_LEADER) & (np.arange(G) // 256 == 3))
     assert len(lead)
@@ -233,6 +254,10 @@ def _handover_class(x):
 @pytest.mark.parametrize("storm", [None, "0"])
 @pytest.mark.parametrize("n", [5, 7])
 def test_storm_handover_class_boundaries(n, storm, monkeypatch):
+    run_storm_handover_class_boundaries(n, storm, monkeypatch)
+
+
+def run_storm_handover_class_boundaries(n, storm, monkeypatch, lift=None, make=Pair):
     """The edges of the storm hand-over rule (handover_class: what k_apply_lead
     does with a group before its first message, and so which partitions k_route
     closes), three partitions of 256 groups, every group with messages, no
@@ -255,6 +280,7 @@ def test_storm_handover_class_boundaries(n, storm, monkeypatch):
             g[x], runs[x] = lead[x], lruns[x]
         if cls[x] == "nc":
             g[x]["commit_zero"] = 1
+    g, runs, _ = lifted(lift, g, runs, delta=2048, eps=500)
     hb = abi.HB_MSG_HEARTBEAT_RESP
     rows = []  # (group, its k-th message, info, term)
     for x in range(G):
@@ -274,7 +300,7 @@ def test_storm_handover_class_boundaries(n, storm, monkeypatch):
     rows = rows[order]
     b = dict(group=rows[:, 0].astype(np.uint32), info=rows[:, 2].astype(np.uint32), term=rows[:, 3].copy(),
              index=np.zeros(len(rows), np.uint64), hint=None, props=None)
-    pair = Pair(g, runs, n, 8, max_batch=1 << 13)
+    pair = make(g, runs, n, 8, max_batch=1 << 13)
     removed = np.array([x for x in range(G) if cls[x] == "removed"])
     for x in removed:
         pair.eng.remove_groups(int(x), 1)
@@ -289,7 +315,7 @@ def test_storm_handover_class_boundaries(n, storm, monkeypatch):
     pair.eng.get_groups = groups_but_removed
     for k in range(2):
         _, st, _ = pair.step(dict(b, term=synth.storm_terms(b["term"], k)), ctx=f"hand-over classes {k}")
-        assert bool(pair.eng.step_kernels() & abi.HB_KERN_ROUTE_ELECT) == (storm is None)
+        assert not pair.gpu or bool(pair.eng.step_kernels() & abi.HB_KERN_ROUTE_ELECT) == (storm is None)
         assert st[abi.HB_STAT_WON] > 0 and st[abi.HB_STAT_LOST] > 0
 
 
@@ -313,12 +339,17 @@ DRAWS = np.random.default_rng(77).integers(0, 1 << 63, 4096, dtype=np.uint64)
 
 @pytest.mark.parametrize("seed,nmax,W", [(31, 3, 8), (32, 5, 8), (33, 7, 16)])
 def test_tick_random_states(seed, nmax, W):
+    run_tick_random_states(seed, nmax, W)
+
+
+def run_tick_random_states(seed, nmax, W, lift=None, make=Pair):
     """Ticks interleaved with batches over every role (leaders beat, followers
     and candidates time out on their own draw positions, non-promotable nodes
     stay at 0); steps zero r.elapsed on every reset."""
     G = 2000
     g, runs, ins = synth.random_groups(G, nmax, seed=seed, W=W)
-    pair = Pair(g, runs, nmax, W, ins=ins, max_batch=1 << 15)
+    g, runs, ins = lifted(lift, g, runs, ins, delta=24, eps=20)
+    pair = make(g, runs, nmax, W, ins=ins, max_batch=1 << 15)
     pair.set_timers(synth.random_timers(G, seed=seed + 1, et_hi=6, ht_hi=3), DRAWS)
     for k in range(12):
         pair.tick(ctx=f"tick {seed}/{k}")
@@ -327,10 +358,15 @@ def test_tick_random_states(seed, nmax, W):
 
 
 def test_tick_elections_and_heartbeats():
+    run_tick_elections_and_heartbeats()
+
+
+def run_tick_elections_and_heartbeats(lift=None, make=Pair):
     """cfg4-shaped followers time out and campaign; the winners then beat."""
     G = 3000
     g, runs = synth.election_groups(G, 5, seed=41)
-    pair = Pair(g, runs, 5, 64, max_batch=1 << 16)
+    g, runs, _ = lifted(lift, g, runs, delta=1 << 15, eps=500)
+    pair = make(g, runs, 5, 64, max_batch=1 << 16)
     t = np.zeros(G, abi.TIMER_DTYPE)
     t["election_tick"], t["heartbeat_tick"] = 4, 2
     pair.set_timers(t, DRAWS)
@@ -389,6 +425,10 @@ def test_general_kernel_slot_boundary(nmax):
 @pytest.mark.parametrize("seed,nmax,W,max_size", [(61, 3, 8, 40), (62, 5, 16, 150), (63, 7, 8, 1000),
                                                   (64, 5, 256, 1)])
 def test_fuzz_finite_max_msg_size(seed, nmax, W, max_size):
+    run_fuzz_finite_max_msg_size(seed, nmax, W, max_size)
+
+
+def run_fuzz_finite_max_msg_size(seed, nmax, W, max_size, lift=None, make=Pair):
     """A finite MaxSizePerMsg (raft/raft.go:265 + limitSize raft/util.go:97-110):
     fuzzed states and messages, MsgProps and dense proposals carrying entries of
     random payload sizes; every MsgApp's last entry (optimisticUpdate /
@@ -396,8 +436,9 @@ def test_fuzz_finite_max_msg_size(seed, nmax, W, max_size):
     caller loaded only part of the log's sizes fault HB_FAULT_SIZE_WINDOW (the
     engine's precondition) on both sides where a send reaches below them."""
     g, runs, ins = synth.random_groups(1200, nmax, seed=seed, W=W)
+    g, runs, ins = lifted(lift, g, runs, ins, delta=24, eps=20)
     sizes = synth.window_sizes(g, runs, seed=seed + 1)
-    pair = Pair(g, runs, nmax, W, ins=ins, max_msg_size=max_size, sizes=sizes, max_batch=1 << 14)
+    pair = make(g, runs, nmax, W, ins=ins, max_msg_size=max_size, sizes=sizes, max_batch=1 << 14)
     for k in range(3):
         b = synth.attach_entry_descs(synth.random_batch(g, 5000, seed=seed + 10 * k), len(g), seed=seed + 7 * k)
         pair.step(b, ctx=f"finite max size {max_size} step {k}")
@@ -444,6 +485,10 @@ def _multinode_leader_batch(g, rng, last, ents):
 
 @pytest.mark.parametrize("sized", [False, True])
 def test_msgprop_messages_on_fast_lane(sized):
+    run_msgprop_messages_on_fast_lane(sized)
+
+
+def run_msgprop_messages_on_fast_lane(sized, lift=None, make=Pair):
     """HB_STEP_MSG_PROPS (n = 3, a third route slot): a leader's two acks and
     the application's MsgProp of 1-3 entries, as a MultiNode cycle sends them,
     stay on the fast lane (stepLeader MsgProp -> appendEntry -> maybeCommit ->
@@ -452,8 +497,9 @@ def test_msgprop_messages_on_fast_lane(sized):
     every type with the flag set."""
     G, n = 3000, 3
     g, runs = synth.steady_groups(G, n, seed=141, last_hi=1 << 12)
+    g, runs, _ = lifted(lift, g, runs, delta=2048, eps=500)
     kw = dict(max_msg_size=256, sizes=synth.window_sizes(g, runs, seed=142, frac_full=1.0)) if sized else {}
-    pair = Pair(g, runs, n, 256, max_batch=4 * G, **kw)
+    pair = make(g, runs, n, 256, max_batch=4 * G, **kw)
     rng = np.random.default_rng(143)
     last = g["last_index"].astype(np.int64).copy()
     for step in range(3):
@@ -474,6 +520,10 @@ def test_msgprop_messages_on_fast_lane(sized):
 # ---------------------------------------------------------------- follower side
 @pytest.mark.parametrize("seed,nmax,W", [(71, 3, 8), (72, 5, 16), (73, 7, 8), (74, 3, 256)])
 def test_fuzz_follower_side(seed, nmax, W):
+    run_fuzz_follower_side(seed, nmax, W)
+
+
+def run_fuzz_follower_side(seed, nmax, W, lift=None, make=Pair):
     """MsgApp (entries, conflicts, rejections), MsgHeartbeat, MsgSnap (restore /
     fast-forward / ignore) and MsgVote (grant / reject, senders outside prs)
     interleaved with every leader-side message type: k_apply hands a group over
@@ -481,7 +531,8 @@ def test_fuzz_follower_side(seed, nmax, W):
     (responses, appends, restores), statistics, records, inflights and timers
     (the follower side zeroes r.elapsed) equal the oracle's."""
     g, runs, ins = synth.random_groups(1500, nmax, seed=seed, W=W)
-    pair = Pair(g, runs, nmax, W, ins=ins, max_batch=1 << 15, term_runs=True)
+    g, runs, ins = lifted(lift, g, runs, ins, delta=24, eps=20)
+    pair = make(g, runs, nmax, W, ins=ins, max_batch=1 << 15, term_runs=True)
     pair.set_timers(synth.random_timers(len(g), seed=seed), DRAWS)
     now = pair.og.groups()
     for k in range(4):
@@ -594,6 +645,10 @@ def _merge_follow(a, b, seed):
 
 # ---------------------------------------------------------------- the log index at depth
 def test_deep_lag_finite_max_msg_size():
+    run_deep_lag_finite_max_msg_size()
+
+
+def run_deep_lag_finite_max_msg_size(lift=None, make=Pair):
     """etcdserver's MaxSizePerMsg = 1 MiB (etcdserver/raft.go:229) with
     followers 5,000+ entries behind leaders whose logs hold 6,000-9,000
     entries of random payload sizes: heartbeat responses, rejections
@@ -604,8 +659,9 @@ def test_deep_lag_finite_max_msg_size():
     records and inflights equal the oracle's."""
     G, n = 500, 3
     g, runs = synth.deep_lag_leaders(G, n, seed=91)
+    g, runs, _ = lifted(lift, g, runs, delta=7000, eps=20)
     sizes = synth.window_sizes(g, runs, seed=92, max_len=900, frac_full=1.0)
-    pair = Pair(g, runs, n, 64, max_msg_size=1 << 20, sizes=sizes, max_batch=1 << 14)
+    pair = make(g, runs, n, 64, max_msg_size=1 << 20, sizes=sizes, max_batch=1 << 14)
     rng = np.random.default_rng(93)
     for step in range(4):
         now = pair.og.groups()
@@ -618,7 +674,9 @@ def test_deep_lag_finite_max_msg_size():
                 if u < 0.35:  # MsgHeartbeatResp: Match < lastIndex -> sendAppend
                     t, x, h = abi.HB_MSG_HEARTBEAT_RESP, 0, 0
                 elif u < 0.6:  # reject of the last probe, follower far behind
-                    t, x, h = abi.HB_MSG_APP_RESP, int(p["next"]) - 1, int(rng.integers(0, max(1, int(p["next"]))))
+                    lo = int(now[i]["first_index"]) - 1  # (0 here; a lifted log starts higher)
+                    h = lo + int(rng.integers(0, max(1, int(p["next"]) - lo)))
+                    t, x = abi.HB_MSG_APP_RESP, int(p["next"]) - 1
                     rej = 1
                 else:  # ack of what was sent (or a stale ack)
                     t, x, h = abi.HB_MSG_APP_RESP, max(int(p["next"]) - 1, int(p["match"])), 0
@@ -634,8 +692,9 @@ def test_deep_lag_finite_max_msg_size():
         b = synth.attach_entry_descs(b, G, seed=94 + step, max_len=900)
         _, st, ora = pair.step(b, ctx=f"deep lag step {step}")
         assert st[abi.HB_STAT_FAULTS] == 0 and (ora["fault"] == 0).all()
-    sc, rc = pair.eng.log_capacity(0)
-    assert sc >= 6000 and rc >= abi.HB_TERM_RING_MIN
+    if pair.gpu:
+        sc, rc = pair.eng.log_capacity(0)
+        assert sc >= 6000 and rc >= abi.HB_TERM_RING_MIN
 
 
 @pytest.mark.parametrize("seed,nmax", [(95, 3), (96, 5)])
@@ -701,26 +760,32 @@ def test_fuzz_commit_zero(seed, nmax, W):
 
 
 def test_fast_lanes_hand_over_commit_zero_groups():
+    run_fast_lanes_hand_over_commit_zero_groups()
+
+
+def run_fast_lanes_hand_over_commit_zero_groups(lift=None, make=Pair):
     """The steady-state streams (cfg2 leaders on the fast lane, follow on the
     follower lane) over groups half of which still have r.Commit = 0: those are
     stepped by the general lane, whose first Step clears the flag; a follower
     receiving a MsgApp below committed answers with r.Commit (0 -> maybeAppend's
     match, or committed once stepped)."""
     g, runs = synth.steady_groups(4096, 3, seed=41, last_hi=1 << 12)
+    g, runs, _ = lifted(lift, g, runs, delta=2048, eps=500)
     g["commit_zero"] = (np.arange(4096) % 2).astype(np.uint32)
-    pair = Pair(g, runs, 3, 256, max_batch=1 << 15)
+    pair = make(g, runs, 3, 256, max_batch=1 << 15)
     _, st, now = pair.step(synth.cfg2_batch(g, 0, seed=42), ctx="cfg2 commit_zero")
     assert st[abi.HB_STAT_COMMITS] == 4096 and not now["commit_zero"].any()
     f, fruns = synth.follow_groups(4096, 3, seed=43, last_hi=1 << 12, with_runs=True)
+    f, fruns, _ = lifted(lift, f, fruns, delta=2048, eps=500)
     f["commit_zero"] = (np.arange(4096) % 2).astype(np.uint32)
-    pair = Pair(f, fruns, 3, 256, max_batch=1 << 15, term_runs=True)
+    pair = make(f, fruns, 3, 256, max_batch=1 << 15, term_runs=True)
     b = synth.follow_batch(f, 0, seed=44)
     _, st, now = pair.step(b, ctx="follow commit_zero")
     assert not now["commit_zero"].any()
     # an empty MsgApp below committed: r.Commit = 0 takes maybeAppend's match
     # (MsgAppResp{Index: m.Index}); r.Commit = committed answers with it
     f["commit_zero"] = (np.arange(4096) % 2).astype(np.uint32)
-    pair = Pair(f, fruns, 3, 256, max_batch=1 << 15, term_runs=True)
+    pair = make(f, fruns, 3, 256, max_batch=1 << 15, term_runs=True)
     grp = np.nonzero(f["committed"] >= 2)[0].astype(np.uint32)
     n = len(grp)
     com = f["committed"][grp].astype(np.uint64)

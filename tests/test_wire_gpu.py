@@ -8,6 +8,7 @@ from etcd_amd import abi, synth
 from oracle.pyoracle import decode_batch
 
 from . import wire_util as W
+from .lift_util import lifted
 from .parity_util import Pair, assert_events_equal, assert_groups_equal
 
 pytestmark = pytest.mark.gpu
@@ -70,12 +71,66 @@ def test_decode_corpus_bit_exact(seed):
     assert counts[abi.HB_WIRE_OK] > 0 and counts[abi.HB_WIRE_ERROR] > 0 and counts[abi.HB_WIRE_PANIC] > 0
 
 
+# every varint length of a u64: 2^(7k) - 1 is the largest value of k bytes, 2^(7k) the smallest of k + 1
+EDGES = sorted({v for k in range(1, 10) for v in ((1 << 7 * k) - 1, 1 << 7 * k)} | {1 << 63, (1 << 64) - 1})
+
+
+def test_decode_full_width_varints():
+    """Well-formed responses of the three types whose Term, Index, RejectHint,
+    Commit and LogTerm take every varint-length edge of a u64 (1 to 10 bytes,
+    2^63 and 2^64 - 1 included): each field sweeps the edges while the others
+    hold edge values of other lengths, rejecting and not.  Status and every
+    field of the batch record equal the oracle's decode of the same bytes, and
+    the decoded Term / Index / RejectHint are the encoded values."""
+    import torch
+    from etcd_amd.hipbatch import Engine
+    G = 64
+    g, _ = synth.steady_groups(G, 3, seed=3, with_runs=False)
+    eng = Engine(G, max_replicas=3, max_inflight=8, max_batch=1 << 12)
+    eng.load_groups(g)
+    peers = _peers(G, 3)
+    eng.load_peers(peers)
+    E = len(EDGES)
+    recs, want = [], []
+    fields = ("term", "index", "hint", "commit", "log_term")
+    for t in W.RESP_TYPES:
+        for fi, f in enumerate(fields):
+            for k, v in enumerate(EDGES):
+                for rej in (False, True):
+                    # the swept field takes v, the others the edges 3, 7, 11, ... places further on
+                    kw = {o: EDGES[(k + 3 + 4 * ((fi + j) % 5)) % E] for j, o in enumerate(fields)}
+                    kw[f] = v
+                    recs.append(W.gogo_marshal(t, to=1, frm=1 + (k + fi) % 3, reject=rej, **kw))
+                    want.append((kw["term"], kw["index"], kw["hint"]))
+    assert len(recs) == 3 * 5 * E * 2 and {len(W.varint(v)) for v in EDGES} == set(range(1, 11))
+    grp = (np.arange(len(recs)) % G).astype(np.uint32)
+    data, off, ln = W.pack(recs)
+    out, status = _decode_dev(eng, torch, data, off, ln, grp)
+    ora = decode_batch(data, off, ln, grp, G, np.full(G, 3, np.uint32), peers)
+    st = status.cpu().numpy()
+    assert (ora["status"] == abi.HB_WIRE_OK).all()
+    assert np.array_equal(st, ora["status"])
+    for k, dt in (("group", np.uint32), ("info", np.uint32), ("term", np.uint64), ("index", np.uint64),
+                  ("hint", np.uint64)):
+        d = out[k].cpu().numpy().view(dt)
+        bad = np.nonzero(d != ora[k])[0]
+        assert len(bad) == 0, f"{k} differs at {bad[:5]}: dev {d[bad[:5]]} ora {ora[k][bad[:5]]}"
+    want = np.array(want, dtype=np.uint64)
+    assert np.array_equal(ora["term"], want[:, 0]) and np.array_equal(ora["index"], want[:, 1])
+    assert np.array_equal(ora["hint"], want[:, 2])
+
+
 def test_decode_then_step_cfg2():
+    run_decode_then_step_cfg2()
+
+
+def run_decode_then_step_cfg2(lift=None):
     """cfg2 acks as the reference encodes them -> hb_decode -> hb_step equals
     the oracle stepping its own decode of the same bytes."""
     import torch
     G, n = 4000, 3
     g, runs = synth.steady_groups(G, n, seed=5)
+    g, runs, _ = lifted(lift, g, runs, delta=1 << 19, eps=500)
     pair = Pair(g, runs, n, 256, max_batch=G * n + 16)
     peers = _peers(G, n)
     pair.eng.load_peers(peers)
