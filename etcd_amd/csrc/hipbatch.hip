@@ -128,7 +128,7 @@ static_assert(SIS_LOG_MAX3 <= 7, "a record carries its partition in the bucket i
 // each on a 128-byte line of its own (CTR_STRIDE words): the returning atomics of every partition
 // on one line serialise at the memory side (~7 ns each; 16K partitions put 16K on a list)
 enum : uint32_t { CTR_STRIDE = 32, CTR_AP = 0, CTR_EL = 8 * CTR_STRIDE, CTR_FL = 16 * CTR_STRIDE,
-                  CTR_DONE = 17 * CTR_STRIDE, CTR_WORDS = 18 * CTR_STRIDE };
+                  CTR_DONE = 17 * CTR_STRIDE, CTR_STEADY = 18 * CTR_STRIDE, CTR_WORDS = 19 * CTR_STRIDE };
 // step statistics: NSH shards per value, each (value, shard) on a 128-byte line of its own
 constexpr uint32_t NSH = 8;
 constexpr uint64_t STAGE_MAX = 8ull << 20;  // host-pointer batches packed into one pinned copy up to this size  // (a shard per XCD slot; a finish lane per (value, shard))
@@ -870,6 +870,9 @@ struct ApplyArgs {
   uint32_t nmax;            // the handle's replica bound (5 or 7)
   uint32_t storm;           // 2: this step's route closes such partitions (lskip), 0: it does not
   uint8_t* lskip;           // [NB] 1: the route closed the partition
+  // the n = 3 fast lane's wave-uniform steady path (SteadyLane, hipbatch_fast.h)
+  uint32_t steady;          // 1: a wave of steady / idle lanes takes it (HB_FAST_STEADY=0 at hb_create: never)
+  uint32_t* steady_cnt;     // tests (HB_FAST_STEADY_COUNT=1): group-waves that took it this step; else null
 };
 
 // Message slots k_route keeps per group: n - 1 (one MsgAppResp per follower,
@@ -1512,14 +1515,16 @@ __global__ void __launch_bounds__(ROUTE_THREADS) k_route(ApplyArgs a) {
 // than slots and no proposal is handed over with its state unloaded.
 // fol (X mode): a follower whose messages all sit in its slots, stepped by
 // FollowLane as far as it takes them (s_h / s_c: m.LogTerm, m.Commit).
-template <int NMAX, uint32_t KS>
+// STEADY (n = 3, two slots, not X mode): a wave whose lanes are all steady or
+// idle runs SteadyLane instead (a.steady; `nsteady` counts those waves).
+template <int NMAX, uint32_t KS, bool STEADY = false>
 __device__ __forceinline__ bool fast_step(const ApplyArgs& a, FollowLane<NMAX>& L, uint32_t part, uint32_t lane,
                                           bool live, bool lead, bool leader, bool fol, uint32_t prop_raw, uint32_t cnt,
                                           uint32_t (&s_info)[KS], uint32_t (&s_orig)[KS],
                                           uint64_t (&s_term)[KS], uint64_t (&s_index)[KS],
                                           uint64_t (&s_h)[KS], uint64_t (&s_c)[KS],
                                           uint64_t moff, uint32_t* l_pfill, uint32_t* l_fill, uint32_t* l_flag,
-                                          uint32_t* l_eflag, uint32_t (&vals)[ST_N + 1]) {
+                                          uint32_t* l_eflag, uint32_t (&vals)[ST_N + 1], uint32_t& nsteady) {
   constexpr uint32_t KMAX = KS;
   const uint32_t g = part * PART + lane;
   const uint64_t last0 = L.last, commit0 = L.committed;
@@ -1532,9 +1537,70 @@ __device__ __forceinline__ bool fast_step(const ApplyArgs& a, FollowLane<NMAX>& 
   // slot of ev_per_msg x PART words), before any message event of the group.
   const uint64_t poff = (uint64_t)part * PART * a.ev_per_msg;
   if (lane == 0) a.ev_off[2 * part] = poff;
+  const uint32_t prop_k = live ? prop_raw : 0u;
+  if constexpr (STEADY) {
+    static_assert(NMAX == 3 && KS == 2, "SteadyLane is the n = 3, two-slot lane");
+    if (a.steady) {  // (uniform)
+      // idle: nothing is stepped and nothing stored below (not live; or no
+      // proposal and no message, and a loaded leader's load / store are
+      // no-ops: M_RS clear, self a slot).  A live non-leader with work is
+      // neither: it is handed over.
+      const bool work = live && (prop_k != 0 || cnt != 0);
+      const bool idle = !work && (!lead || (!(L.mlo & (uint32_t)M_RS) && L.self() < 3));
+      SteadyLane P;
+      P.ok = false;
+      P.evm = 0;
+      if (lead && work) P.plan(L, prop_k, cnt, s_info, s_orig, s_term, s_index);
+      const bool steady = lead && work && P.ok;
+      if (__ballot(!(steady || idle)) == 0) {
+        // a lane's words are known: one LDS add per wave and chunk, the words
+        // of one kind side by side (a group's words keep their order)
+        const uint32_t evm = steady ? P.evm : 0u;
+        uint32_t tot = 0, base = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < SteadyLane::EW_P; ++j) tot += (uint32_t)__popcll(__ballot((evm >> j) & 1u));
+        if (tot && (lane & 63) == 0) base = atomicAdd(l_pfill, tot);
+        base = __builtin_amdgcn_readfirstlane(base);
+        uint64_t* chunk = a.ev + poff;
+#pragma unroll
+        for (uint32_t j = 0; j < SteadyLane::EW_P; ++j) {
+          const uint64_t m = __ballot((evm >> j) & 1u);
+          if ((evm >> j) & 1u) chunk[base + mbcnt64(m)] = P.word(j, lane);
+          base += (uint32_t)__popcll(m);
+        }
+        tot = 0;
+        base = 0;
+#pragma unroll
+        for (uint32_t j = SteadyLane::EW_P; j < SteadyLane::EW; ++j) tot += (uint32_t)__popcll(__ballot((evm >> j) & 1u));
+        if (tot && (lane & 63) == 0) base = atomicAdd(l_fill, tot);
+        base = __builtin_amdgcn_readfirstlane(base);
+        chunk = a.ev + moff;
+#pragma unroll
+        for (uint32_t j = SteadyLane::EW_P; j < SteadyLane::EW; ++j) {
+          const uint64_t m = __ballot((evm >> j) & 1u);
+          if ((evm >> j) & 1u) chunk[base + mbcnt64(m)] = P.word(j, lane);
+          base += (uint32_t)__popcll(m);
+        }
+        if (steady) P.commit(L);
+        // (no lane is flagged: resume, commit0, cnt and the slots are not
+        // written, and the partition's hand-over bits stay 0)
+        vals[ST_MSGS] = steady ? cnt : 0u;
+        vals[ST_APPRESP] = steady ? cnt : 0u;
+        vals[ST_VOTERESP] = 0;
+        vals[ST_DROPPED] = 0;
+        vals[ST_COMMITS] = (uint32_t)(steady && P.committed != commit0);
+        vals[ST_WON] = 0;
+        vals[ST_LOST] = 0;
+        vals[ST_FAULTS] = 0;
+        vals[ST_ENTRIES] = steady ? (uint32_t)(P.last - last0) : 0u;
+        vals[ST_N] = steady ? P.nev() : 0u;
+        if (a.steady_cnt && __ballot(g < a.S.G) != 0) ++nsteady;  // (tests; a wave of grid padding is not counted)
+        return false;
+      }
+    }
+  }
   L.E.chunk = a.ev + poff;
   L.E.fill = l_pfill;
-  const uint32_t prop_k = live ? prop_raw : 0u;
   if (prop_k) {
     if (lead && L.prop_ok(prop_k)) {
       L.arrival = 0xFFFFFFFFu;
@@ -1692,13 +1758,14 @@ __global__ void __launch_bounds__(PART, HB_FAST_WAVES) k_apply_fast(ApplyArgs a)
   __shared__ uint32_t l_flag[FLAG_WORDS];
   __shared__ uint32_t l_eflag[FLAG_WORDS];
   __shared__ uint64_t l_stats[ST_N + 1];
+  __shared__ uint32_t l_steady;
 
   const uint32_t part = block_part(a.sis_log);
   if (part >= a.NB) return;  // uniform: grid padding
   const uint32_t tid = threadIdx.x;
   const uint32_t g = part * PART + tid;
   const bool gvalid = g < a.S.G;
-  if (tid == 0) l_fill = l_pfill = 0;
+  if (tid == 0) l_fill = l_pfill = l_steady = 0;
   if (tid <= ST_N) l_stats[tid] = 0;
   if (tid < FLAG_WORDS) l_flag[tid] = l_eflag[tid] = 0;
 
@@ -1760,9 +1827,14 @@ __global__ void __launch_bounds__(PART, HB_FAST_WAVES) k_apply_fast(ApplyArgs a)
     s_c[k] = (uint64_t)x.z | ((uint64_t)x.w << 32);
   }
   uint32_t vals[ST_N + 1];
-  (void)fast_step<NMAX, KMAX>(a, L, part, tid, live, lead, leader, fol, prop_raw, cnt, s_info, s_orig, s_term, s_index, s_h,
-                        s_c, a.ev_off[2 * part + 1], &l_pfill, &l_fill, l_flag, l_eflag, vals);
+  constexpr bool STEADY = NMAX == 3 && KMAX == 2 && !X;
+  uint32_t nsteady = 0;
+  (void)fast_step<NMAX, KMAX, STEADY>(a, L, part, tid, live, lead, leader, fol, prop_raw, cnt, s_info, s_orig, s_term,
+                                      s_index, s_h, s_c, a.ev_off[2 * part + 1], &l_pfill, &l_fill, l_flag, l_eflag, vals,
+                                      nsteady);
+  if (STEADY && a.steady_cnt && nsteady && (tid & 63) == 0) atomicAdd(&l_steady, nsteady);
   reduce_stats(a, l_stats, vals);
+  if (STEADY && a.steady_cnt && tid == 0 && l_steady) atomicAdd(a.steady_cnt, l_steady);
   if (tid < FLAG_WORDS) a.pflag[(size_t)part * FLAG_WORDS + tid] = l_flag[tid];
   if constexpr (NMAX >= 5) {
     if (tid < FLAG_WORDS) a.eflag[(size_t)part * FLAG_WORDS + tid] = l_eflag[tid];
@@ -1891,16 +1963,27 @@ __global__ void __launch_bounds__(RF_THREADS, HB_RF_WAVES) k_route_fast(ApplyArg
       a.ev_off[2 * part + 1] = mo;
     }
     l_moff[tid] = mo;
+    l_ptot[tid] = 0;  // (read above: word 0 now counts the steady group-waves, a.steady_cnt)
   }
   __syncthreads();
   // ---- the fast lane (as k_apply_fast) over the workgroup's groups, RG / RF_THREADS per lane
   uint32_t acc[ST_N + 1];
 #pragma unroll
   for (int k = 0; k <= ST_N; ++k) acc[k] = 0;
+  constexpr bool STEADY = KMAX == 2 && !X;
+  uint32_t nsteady = 0;
   for (uint32_t i = tid; i < RG; i += RF_THREADS) {
-    const uint32_t p = i >> PART_LOG, part = part0 + p, lane = i & (PART - 1);
+    // (a wave's 64 groups lie in one partition: with the steady path the
+    // partition and its M chunk are kept as scalars, which frees the lane
+    // registers the two paths need side by side)
+    const uint32_t p = STEADY ? (uint32_t)__builtin_amdgcn_readfirstlane(i >> PART_LOG) : i >> PART_LOG;
+    const uint32_t part = part0 + p, lane = i & (PART - 1);
     const uint32_t g = part * PART + lane;
     const bool gvalid = part < a.NB && g < G;
+    uint64_t moff = l_moff[p];
+    if constexpr (STEADY)
+      moff = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)moff) |
+             (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(moff >> 32)) << 32;
     FollowLane<NMAX> L;
     L.S = a.S;
     L.g = g;
@@ -1939,11 +2022,14 @@ __global__ void __launch_bounds__(RF_THREADS, HB_RF_WAVES) k_route_fast(ApplyArg
       s_c[k] = (uint64_t)xe.z | ((uint64_t)xe.w << 32);
     }
     uint32_t vals[ST_N + 1];
-    const bool flagged = fast_step<NMAX, KMAX>(a, L, part, lane, live, lead, leader, fol, prop_raw, cnt, s_info, s_orig,
-                                               s_term, s_index, s_h, s_c, l_moff[p], &l_pfill[p], &l_fill[p], l_flag[p],
-                                               nullptr, vals);
+    const bool flagged = fast_step<NMAX, KMAX, STEADY>(a, L, part, lane, live, lead, leader, fol, prop_raw, cnt, s_info,
+                                                       s_orig, s_term, s_index, s_h, s_c, moff, &l_pfill[p],
+                                                       &l_fill[p], l_flag[p], nullptr, vals, nsteady);
+    // (two slots, not X mode: only a leader's messages are stepped here and
+    // each is a MsgAppResp, so that sum is the message sum: one register less)
 #pragma unroll
-    for (int k = 0; k <= ST_N; ++k) acc[k] += vals[k];
+    for (int k = 0; k <= ST_N; ++k)
+      if (!(STEADY && k == ST_APPRESP)) acc[k] += vals[k];
     if (flagged) {  // what k_apply reads of a group it takes over: its count and slots
       a.cnt[g] = (uint8_t)cnt;
 #pragma unroll
@@ -1955,7 +2041,10 @@ __global__ void __launch_bounds__(RF_THREADS, HB_RF_WAVES) k_route_fast(ApplyArg
       }
     }
   }
+  if constexpr (STEADY) acc[ST_APPRESP] = acc[ST_MSGS];
+  if (STEADY && a.steady_cnt && nsteady && (tid & 63) == 0) atomicAdd(&l_ptot[0], nsteady);
   reduce_stats(a, l_stats, acc);  // (ends with a barrier: the partitions' fills and flags are final)
+  if (STEADY && a.steady_cnt && tid == 0 && l_ptot[0]) atomicAdd(a.steady_cnt, l_ptot[0]);
   for (uint32_t j = tid; j < NP * FLAG_WORDS; j += RF_THREADS) {
     const uint32_t p = j / FLAG_WORDS, part = part0 + p;
     if (part < a.NB) a.pflag[(size_t)part * FLAG_WORDS + j % FLAG_WORDS] = l_flag[p][j % FLAG_WORDS];
@@ -3575,6 +3664,8 @@ struct hb_handle {
   uint32_t kern = 0;  // hb_step_kernels of the last step
   uint32_t fuse = 2;  // k_route_fast: 0 never, 1 one-pass handles, 2 every geometry (HB_ROUTE_FUSE at hb_create)
   uint32_t storm = 2;  // n >= 5: 2: the route's storm hand-over, 0: off (HB_STORM=0 at hb_create)
+  bool steady = true;        // n = 3 fast lane: the wave-uniform steady path (HB_FAST_STEADY=0 at hb_create: off)
+  bool steady_count = false;  // tests: count the group-waves that take it (HB_FAST_STEADY_COUNT=1 at hb_create)
   uint32_t agrid = 0;  // the apply kernels' grid (apply_grid_for)
   uint32_t bk_bits = 1;            // bits of a bucket id
   // host-pointer staging
@@ -3869,6 +3960,8 @@ int hb_create(int device, uint32_t capacity, uint32_t max_replicas, uint32_t max
   if (const char* e = getenv("HB_SMALL_STEP")) h->no_small = e[0] == '0';
   if (const char* e = getenv("HB_ROUTE_FUSE")) h->fuse = (uint32_t)atoi(e);
   if (const char* e = getenv("HB_STORM")) h->storm = atoi(e) == 0 ? 0u : 2u;
+  if (const char* e = getenv("HB_FAST_STEADY")) h->steady = atoi(e) != 0;
+  if (const char* e = getenv("HB_FAST_STEADY_COUNT")) h->steady_count = atoi(e) != 0;
   const size_t G = capacity, R = h->nmax;
   DevState& s = h->st;
   s.G = capacity;
@@ -4853,6 +4946,8 @@ int hb_step(hb_handle* h, const hb_batch* b, uint32_t flags) {
   aa.slotx = xmode ? ps.slotx : nullptr;
   aa.nmax = h->nmax;
   aa.lskip = h->lskip;
+  aa.steady = h->steady ? 1u : 0u;
+  aa.steady_cnt = h->steady_count ? ps.ctr + CTR_STEADY : nullptr;
   // the route's storm hand-over writes the handle's flags and lists: only when
   // the apply of the previous step is not running beside it (one stream)
   aa.storm = (h->nmax >= 5 && !two && !xmode && !bd.props) ? h->storm : 0u;
@@ -5053,6 +5148,16 @@ int hb_phase_ms(hb_handle* h, float* out, uint32_t* steps) {
 int hb_step_kernels(hb_handle* h, uint32_t* mask) {
   if (!h || !mask) return HB_EINVAL;
   *mask = h->kern;
+  return HB_OK;
+}
+
+int hb_steady_waves(hb_handle* h, uint32_t* n) {
+  if (!h || !n) return HB_EINVAL;
+  *n = 0;
+  if (!h->stepped || !h->steady_count) return HB_OK;
+  DeviceGuard guard(h->device);
+  HB_CHECK(hipStreamSynchronize(h->stream));
+  HB_CHECK(hipMemcpy(n, h->set[h->cur].ctr + CTR_STEADY, 4, hipMemcpyDeviceToHost));
   return HB_OK;
 }
 

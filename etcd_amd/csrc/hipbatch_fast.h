@@ -423,4 +423,239 @@ struct FastLane {
   }
 };
 
+// ---------------------------------------------------------------------------
+// SteadyLane: FastLane<3>::prop + accept + maybe_commit + bcast_append + store
+// for a leader in steady replication, as straight-line code.
+// fast_step runs it for a whole wave when every lane of the wave is steady or
+// has nothing to step; otherwise the wave runs the general FastLane body.
+//
+// plan() steps a copy of the lane's state in registers and clears `ok` at the
+// first thing the specialisation does not cover; nothing is written until
+// the wave has voted, so a lane that turns out not to be steady costs nothing
+// but the vote.  A lane is steady when all of these hold:
+//   * it is a loaded leader (`lead`: live, not M_NC, cnt <= 2 or a proposal)
+//     with n == 3, self < 3, M_RS clear, no size limit (max_msg_size =
+//     HB_NO_LIMIT: a MsgApp carries every entry up to last), cnt <= 2;
+//   * both followers (the two slots that are not self) are Replicate;
+//   * every message passes accept_ok (MsgAppResp, not a reject, Term 0 or the
+//     group's) and comes from a follower, two messages from different ones;
+//   * each ack advances Match and stays inside the log (match < index <=
+//     last) and covers everything sent (Next != 0, index >= Next - 1: free_to
+//     pops the whole window without a ring read);
+//   * no window is full whenever isPaused is asked (each bcastAppend, each
+//     ack), and no follower needs a snapshot (Next >= first);
+//   * a bcastAppend sends both followers the same Index (one EVC_BCAST word)
+//     and leaves both at Next = last + 1, so a later one of the step sends
+//     Index = last and appends nothing to a window;
+//   * maybeCommit advances at most once in the step, inside the log;
+//   * every event's x is below 2^40 (one word per event).
+// The events of such a step are then named by a few values (last, committed,
+// the first bcastAppend's Index) and a mask of which are present, so the lane
+// carries no event words through the vote.  With self known the followers are
+// two values (a < b, slot order), so there is no runtime slot index, no
+// per-message loop, no head copy and no fault, drop or hand-over test.  The
+// events are the words FastLane emits, in the same order per group; commit()
+// writes what FastLane::store would.
+// ---------------------------------------------------------------------------
+struct SteadyFol {
+  uint64_t match, next;
+  uint32_t pm;
+};
+
+struct SteadyLane {
+  // event words: P chunk 0 LAST, 1 COMMIT, 2 EVC_BCAST; M chunk, message t:
+  // 3 + 2t COMMIT, 4 + 2t EVC_BCAST
+  static constexpr uint32_t EW_P = 3, EW = 7;
+  static constexpr uint32_t EVM_BCAST = 0x54, EVM_COMMIT = 0x2A;
+  uint64_t last, committed, tfirst, tlast;
+  uint64_t smatch, snext;  // the self slot
+  uint32_t spm;
+  SteadyFol fa, fb;        // the other two slots, slot order
+  uint32_t spm0, pa0, pb0;  // the three pm words as loaded
+  uint32_t sf, sa, sb;
+  uint32_t evm;            // bit j: event word j is emitted
+  uint32_t ltm;            // bit j (an EVC_BCAST word): its aux, lt_cur of its Index
+  uint32_t jfirst;         // the word of the step's first bcastAppend (0: none yet)
+  uint64_t xfirst;         // its Index (a later one sends last)
+  uint32_t ring_a, ring_b;  // inflights.add's ring position (valid with add_a / add_b)
+  bool add_a, add_b, touch_a, touch_b;  // touch: match / next are written (the slot's dirty bit)
+  bool prop, d_tfirst;
+  bool ok;
+
+  __device__ __forceinline__ uint32_t lt_cur(uint64_t x) const { return (tfirst <= x && x <= tlast) ? 1u : 0u; }
+
+  // send_decide to a Replicate follower; returns the MsgApp's Index
+  __device__ __forceinline__ uint64_t send(SteadyFol& f, uint32_t& ring, bool& add, bool& touch, uint32_t W,
+                                           uint64_t first) {
+    const uint32_t c = pm_count(f.pm);
+    ok = ok && c != W && f.next >= first;
+    const uint64_t x = f.next - 1;
+    if (f.next <= last) {
+      uint32_t idx = pm_start(f.pm) + c;
+      if (idx >= W) idx -= W;
+      ring = idx;  // inflights.add(last)
+      add = true;
+      f.next = last + 1;  // optimisticUpdate
+      touch = true;
+      f.pm = pm_make(HB_PR_REPLICATE, pm_paused(f.pm), pm_start(f.pm), c + 1);
+    }
+    ok = ok && f.next == last + 1;
+    return x;
+  }
+  // bcast_append: both followers are sent to, the same Index; word j
+  __device__ __forceinline__ void bcast(uint32_t W, uint64_t first, uint32_t j) {
+    const uint64_t xa = send(fa, ring_a, add_a, touch_a, W, first);
+    const uint64_t xb = send(fb, ring_b, add_b, touch_b, W, first);
+    ok = ok && xa == xb;
+    if (jfirst == 0) {
+      jfirst = j;
+      xfirst = xa;
+    }  // (else xa == last: both were left at Next = last + 1, and an ack inside the log keeps that)
+    evm |= 1u << j;
+    ltm |= lt_cur(xa) << j;
+  }
+  // maybe_commit over {self, a, b}: the median is the quorum's Match; word j
+  __device__ __forceinline__ bool maybe_commit(uint64_t term, uint64_t first, uint32_t j) {
+    const uint64_t mx = umax64(smatch, fa.match), mn = umin64(smatch, fa.match);
+    const uint64_t mci = umax64(mn, umin64(mx, fb.match));
+    const bool teq = (mci + 1 < first || mci > last) ? term == 0 : (tfirst <= mci && mci <= tlast);
+    const bool up = mci > committed && teq;
+    ok = ok && !(up && (last < mci || (evm & EVM_COMMIT) != 0));
+    if (up) {
+      committed = mci;
+      evm |= 1u << j;
+    }
+    return up;
+  }
+  // accept (after accept_ok) of message t
+  __device__ __forceinline__ void ack(uint32_t info, uint64_t mterm, uint64_t index, uint64_t term, uint32_t W,
+                                      uint64_t first, uint32_t t) {
+    const uint32_t type = info & 0xF, from = (info >> 4) & 0xF;
+    const bool reject = (info >> 8) & 1u;
+    ok = ok && type == HB_MSG_APP_RESP && !reject && (mterm == 0 || mterm == term) && (from == sa || from == sb);
+    const bool isa = from == sa;
+    const uint64_t am = fa.match, an = fa.next, bm = fb.match, bn = fb.next;
+    const uint32_t ap = fa.pm, bp = fb.pm;
+    const uint64_t m0 = isa ? am : bm, nx0 = isa ? an : bn;
+    const uint32_t p0 = isa ? ap : bp;
+    const uint32_t c = pm_count(p0);
+    ok = ok && c != W && m0 < index && index <= last && nx0 != 0 && index >= nx0 - 1;
+    const uint64_t nx = umax64(nx0, index + 1);
+    uint32_t idx = pm_start(p0) + c;  // freeTo: the whole window
+    if (c != 0 && idx >= W) idx -= W;
+    const uint32_t p = pm_make(HB_PR_REPLICATE, 0, idx, 0);
+    fa.match = isa ? index : am;  // maybeUpdate
+    fa.next = isa ? nx : an;
+    fa.pm = isa ? p : ap;
+    touch_a = touch_a || isa;
+    fb.match = isa ? bm : index;
+    fb.next = isa ? bn : nx;
+    fb.pm = isa ? bp : p;
+    touch_b = touch_b || !isa;
+    if (maybe_commit(term, first, EW_P + 2 * t)) bcast(W, first, EW_P + 2 * t + 1);
+  }
+
+  // Steps the lane's proposal and its (at most two) messages on a copy of L.
+  __device__ __forceinline__ void plan(const FastLane<3>& L, uint32_t prop_k, uint32_t cnt,
+                                       const uint32_t (&s_info)[2], const uint32_t (&s_orig)[2],
+                                       const uint64_t (&s_term)[2], const uint64_t (&s_index)[2]) {
+    const uint32_t W = L.S.W;
+    last = L.last;
+    committed = L.committed;
+    tfirst = L.tfirst;
+    tlast = L.tlast;
+    sf = L.self();
+    sa = sf == 0 ? 1u : 0u;
+    sb = sf == 2 ? 1u : 2u;
+    // (selects on values: a conditional on the array elements themselves is a
+    // runtime address, and the lane's registers become scratch)
+    const uint64_t m0 = L.match[0], m1 = L.match[1], m2 = L.match[2];
+    const uint64_t n0 = L.next[0], n1 = L.next[1], n2 = L.next[2];
+    const uint32_t p0 = L.pm[0], p1 = L.pm[1], p2 = L.pm[2];
+    smatch = sf == 0 ? m0 : (sf == 1 ? m1 : m2);
+    snext = sf == 0 ? n0 : (sf == 1 ? n1 : n2);
+    spm = spm0 = sf == 0 ? p0 : (sf == 1 ? p1 : p2);
+    fa.match = sf == 0 ? m1 : m0;
+    fa.next = sf == 0 ? n1 : n0;
+    fa.pm = pa0 = sf == 0 ? p1 : p0;
+    fb.match = sf == 2 ? m1 : m2;
+    fb.next = sf == 2 ? n1 : n2;
+    fb.pm = pb0 = sf == 2 ? p1 : p2;
+    add_a = add_b = touch_a = touch_b = false;
+    ring_a = ring_b = 0;
+    evm = ltm = jfirst = 0;
+    xfirst = 0;
+    prop = d_tfirst = false;
+    ok = L.n() == 3 && sf < 3 && !(L.mlo & (uint32_t)M_RS) && L.S.max_msg_size == HB_NO_LIMIT && cnt <= 2 &&
+         pm_state(fa.pm) == HB_PR_REPLICATE && pm_state(fb.pm) == HB_PR_REPLICATE;
+    if (prop_k) {  // FastLane::prop
+      prop = true;
+      const uint64_t old = last;
+      last += prop_k;
+      if (tfirst == HB_NO_INDEX) {
+        tfirst = old + 1;
+        d_tfirst = true;
+      }
+      tlast = last;
+      evm |= 1u;
+      if (smatch < last) {
+        smatch = last;
+        spm &= ~PM_PAUSED;
+      }
+      if (snext < last + 1) snext = last + 1;
+      maybe_commit(L.term, L.first, 1);
+      bcast(W, L.first, 2);
+    }
+    // arrival order
+    const uint32_t ia = s_info[0], ib = s_info[1], oa = s_orig[0], ob = s_orig[1];
+    const uint64_t ta = s_term[0], tb = s_term[1], xa = s_index[0], xb = s_index[1];
+    const bool sw = cnt == 2 && ob < oa;
+    const uint32_t i0 = sw ? ib : ia, i1 = sw ? ia : ib;
+    const uint64_t t0 = sw ? tb : ta, t1 = sw ? ta : tb;
+    const uint64_t x0 = sw ? xb : xa, x1 = sw ? xa : xb;
+    if (cnt == 2) ok = ok && ((i0 ^ i1) & 0xF0u) != 0;  // two followers
+    if (cnt >= 1) ack(i0, t0, x0, L.term, W, L.first, 0);
+    if (cnt >= 2) ack(i1, t1, x1, L.term, W, L.first, 1);
+    ok = ok && ((last | xfirst) >> 40) == 0;  // (committed <= last)
+  }
+  // public events (an EVC_BCAST word counts once per follower)
+  __device__ __forceinline__ uint32_t nev() const { return __popc(evm) + __popc(evm & EVM_BCAST); }
+  // event word j (bit j of evm)
+  __device__ __forceinline__ uint64_t word(uint32_t j, uint32_t lane) const {
+    if (j == 0) return evc_word(HB_EV_LAST, 0, 0, lane, last, false);
+    if ((EVM_COMMIT >> j) & 1u) return evc_word(HB_EV_COMMIT, 0, 0, lane, committed, false);
+    return evc_word(EVC_BCAST, (1u << sa) | (1u << sb), (ltm >> j) & 1u, lane, j == jfirst ? xfirst : last, false);
+  }
+
+  // FastLane::store for what plan() changed (meta never changes: M_TL and
+  // M_SM, where set, still hold, so their arrays stay unwritten).
+  __device__ __forceinline__ void commit(const FastLane<3>& L) const {
+    const DevState& S = L.S;
+    const uint32_t g = L.g;
+    if (committed != L.committed) at32(S.commit, g) = committed;
+    if (prop) {
+      at32(S.last, g) = last;
+      if (d_tfirst) at32(S.tfirst, g) = tfirst;
+      if (!(L.mlo & (uint32_t)M_TL)) at32(S.tlast, g) = tlast;
+      if (!(L.mlo & (uint32_t)M_SM)) {
+        at32(S.match, sf * S.G + g) = smatch;
+        at32(S.next, sf * S.G + g) = snext;
+      }
+    }
+    if (spm != spm0) at32(S.pm, sf * S.G + g) = spm;
+    if (touch_a) {
+      at32(S.match, sa * S.G + g) = fa.match;
+      at32(S.next, sa * S.G + g) = fa.next;
+    }
+    if (fa.pm != pa0) at32(S.pm, sa * S.G + g) = fa.pm;
+    if (add_a) *L.ring_at(sa, ring_a) = last;
+    if (touch_b) {
+      at32(S.match, sb * S.G + g) = fb.match;
+      at32(S.next, sb * S.G + g) = fb.next;
+    }
+    if (fb.pm != pb0) at32(S.pm, sb * S.G + g) = fb.pm;
+    if (add_b) *L.ring_at(sb, ring_b) = last;
+  }
+};
+
 }  // namespace hb

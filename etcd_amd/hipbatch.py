@@ -460,6 +460,15 @@ class Engine:
         _check("hb_step_kernels", lib().hb_step_kernels(self.h, C.byref(m)))
         return int(m.value)
 
+    def steady_waves(self):
+        """hb_steady_waves: group-waves of the last step that took the fast lane's
+        steady path (counted only when HB_FAST_STEADY_COUNT=1 was set at create)."""
+        f = lib().hb_steady_waves  # (bound here: an A/B build from before the path has no such symbol)
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]
+        n = C.c_uint32()
+        _check("hb_steady_waves", f(self.h, C.byref(n)))
+        return int(n.value)
+
     def phase_ms(self):
         """(per-phase average ms, number of profiled steps) since phase_reset()."""
         out = np.zeros(abi.HB_PHASE_COUNT, dtype=np.float32)

@@ -611,6 +611,13 @@ int  hb_phase_reset(hb_handle* h);
 #define HB_KERN_ROUTE_FAST 1u
 #define HB_KERN_ROUTE_ELECT 2u
 int  hb_step_kernels(hb_handle* h, uint32_t* mask);
+/* The n = 3 fast lane steps a wave whose 64 groups are all in steady
+ * replication (or have nothing to step) by a straight-line path; HB_FAST_STEADY=0
+ * at hb_create turns that off (same output).  For tests: with
+ * HB_FAST_STEADY_COUNT=1 at hb_create the last hb_step counted the waves of
+ * groups that took the path (waves of grid padding excluded); *n = that
+ * count, 0 when the knob was not set (synchronizes). */
+int  hb_steady_waves(hb_handle* h, uint32_t* n);
 
 /* ---- pinned host memory for cgo callers (Go must not hand Go memory to C
  * that C retains; raft/hipbatch packs batches into these buffers). -------- */
