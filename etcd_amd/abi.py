@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-HB_ABI_VERSION = 6
+HB_ABI_VERSION = 7
 
 HB_OK = 0
 HB_EINVAL = -1
@@ -228,6 +228,23 @@ class hb_batch(C.Structure):
         ("eterm", C.c_void_p),
     ]
 
+
+class hb_out_batch(C.Structure):
+    """Outgoing payload-free messages (hb_egress -> hb_encode), device arrays."""
+    _fields_ = [
+        ("group", C.c_void_p),
+        ("info", C.c_void_p),
+        ("to", C.c_void_p),
+        ("term", C.c_void_p),
+        ("log_term", C.c_void_p),
+        ("index", C.c_void_p),
+        ("commit", C.c_void_p),
+        ("hint", C.c_void_p),
+    ]
+
+
+OUT_BATCH_FIELDS = (("group", "<u4"), ("info", "<u4"), ("to", "<u8"), ("term", "<u8"), ("log_term", "<u8"),
+                    ("index", "<u8"), ("commit", "<u8"), ("hint", "<u8"))
 
 # numpy views of the records (same layout as the ctypes structs)
 PROGRESS_DTYPE = np.dtype([

@@ -28,6 +28,7 @@
 #include "hipbatch_elect.h"
 #include "hipbatch_lead.h"
 #include "hipbatch_wire.h"
+#include "hipbatch_wire_out.h"
 
 using namespace hb;
 
@@ -3553,6 +3554,361 @@ __global__ void __launch_bounds__(1024) k_words_small(const uint32_t* counts, ui
 }
 
 // ============================================================================
+// Wire egress: hb_encode, hb_egress
+// ============================================================================
+// hb_encode: a device batch of payload-free outgoing messages -> the bytes
+// Message.MarshalTo writes (hipbatch_wire_out.h), packed densely in record
+// order.  Pass one sizes the records (block sums), one workgroup scans the
+// sums, pass two writes: the mirror image of k_decode.  A wave's 64 records are
+// one contiguous span of at most 64 x 91 bytes; each lane encodes into the
+// wave's LDS window at its offset, then the wave stores the span with
+// coalesced 16-byte stores and its unaligned head and tail byte by byte:
+// neighbouring waves own neighbouring bytes, so nothing outside the span is
+// read or written.
+struct EncodeArgs {
+  const uint32_t* info;
+  const uint64_t *to, *term, *log_term, *index, *commit, *hint;
+  uint64_t cap;
+  const uint64_t* n_dev;  // null: cap
+  uint64_t self_id;
+  uint8_t* bytes;
+  uint64_t bytes_cap;
+  uint64_t* off;
+  uint8_t* status;
+  uint64_t* total;
+  uint32_t* bsum;   // [blocks] bytes per pass-one workgroup
+  uint64_t* bbase;  // [blocks + 1] their exclusive scan, then the total
+};
+constexpr uint32_t ENC_THREADS = 256;
+constexpr uint32_t ENC_SMALL_THREADS = 512;
+constexpr uint32_t ENC_SMALL_MAX = 16384;  // the small-step rule: one workgroup, one launch
+constexpr uint32_t ENC_WIN = 64 * WO_MAX + 16;  // a wave's span plus the 16-byte phase of its first byte
+static_assert(ENC_WIN % 16 == 0, "the window is read back as uint4");
+
+struct EncRec {
+  uint32_t type;
+  bool reject, host;
+  uint64_t to, term, log_term, index, commit, hint;
+};
+__device__ __forceinline__ uint64_t enc_n(const EncodeArgs& a) {
+  const uint64_t n = a.n_dev ? *a.n_dev : a.cap;
+  return n < a.cap ? n : a.cap;
+}
+// record i and its encoded length (0: past the end, or HB_REF_OTHER: the host knows the id)
+__device__ __forceinline__ uint32_t enc_load(const EncodeArgs& a, uint64_t i, uint64_t n, EncRec* r) {
+  r->host = false;
+  if (i >= n) return 0;
+  const uint32_t info = a.info[i];
+  r->type = info & 0xF;
+  r->reject = (info >> 8) & 1u;
+  r->host = ((info >> 4) & 0xF) == HB_REF_OTHER;
+  if (r->host) return 0;
+  r->to = a.to[i];
+  r->term = a.term[i];
+  r->log_term = a.log_term[i];
+  r->index = a.index[i];
+  r->commit = a.commit[i];
+  r->hint = a.hint[i];
+  return wo_size(r->type, r->to, a.self_id, r->term, r->log_term, r->index, r->commit, r->reject, r->hint);
+}
+
+// One tile of blockDim.x records from i0, whose first byte is `base`: off and
+// status always, the bytes when `write` (uniform).  Returns the tile's bytes.
+__device__ __forceinline__ uint32_t enc_tile(const EncodeArgs& a, uint64_t i0, uint64_t n, uint64_t base, bool write,
+                                             uint4* l_win, uint32_t* sh16) {
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t i = i0 + threadIdx.x;
+  EncRec r;
+  const uint32_t sz = enc_load(a, i, n, &r);
+  uint32_t tot;
+  const uint32_t ex = block_excl_scan(sz, sh16, &tot);
+  const uint64_t p = base + ex;
+  if (i < n) {
+    a.off[i] = p;
+    a.status[i] = r.host ? (uint8_t)HB_WIRE_HOST : (uint8_t)HB_WIRE_OK;
+  }
+  if (!write) return tot;
+  const uint64_t lo = __shfl(p, 0), hi = __shfl(p + sz, 63);  // the wave's span
+  uint4* wwin = l_win + (size_t)wave * (ENC_WIN / 16);
+  uint8_t* win = reinterpret_cast<uint8_t*>(wwin);
+  const uintptr_t A = reinterpret_cast<uintptr_t>(a.bytes) + lo, B = reinterpret_cast<uintptr_t>(a.bytes) + hi;
+  const uintptr_t b16 = A & ~(uintptr_t)15;
+  if (sz)
+    wo_write(win + (A - b16) + (p - lo), r.type, r.to, a.self_id, r.term, r.log_term, r.index, r.commit, r.reject,
+             r.hint);
+  __syncthreads();
+  if (hi > lo) {
+    const uintptr_t A16 = (A + 15) & ~(uintptr_t)15, B16 = B & ~(uintptr_t)15;
+    if (A16 < B16) {
+      const uint32_t nc = (uint32_t)((B16 - A16) >> 4), c0 = (uint32_t)((A16 - b16) >> 4);
+      for (uint32_t c = lane; c < nc; c += 64) reinterpret_cast<uint4*>(A16)[c] = wwin[c0 + c];
+      for (uintptr_t x = A + lane; x < A16; x += 64) *reinterpret_cast<uint8_t*>(x) = win[x - b16];
+      for (uintptr_t x = B16 + lane; x < B; x += 64) *reinterpret_cast<uint8_t*>(x) = win[x - b16];
+    } else {
+      for (uintptr_t x = A + lane; x < B; x += 64) *reinterpret_cast<uint8_t*>(x) = win[x - b16];
+    }
+  }
+  __syncthreads();  // the window is free for the next tile
+  return tot;
+}
+
+__global__ void __launch_bounds__(ENC_THREADS) k_enc_size(EncodeArgs a) {
+  __shared__ uint32_t sh16[16];
+  EncRec r;
+  const uint32_t sz = enc_load(a, (uint64_t)blockIdx.x * ENC_THREADS + threadIdx.x, enc_n(a), &r);
+  uint32_t tot;
+  (void)block_excl_scan(sz, sh16, &tot);
+  if (threadIdx.x == 0) a.bsum[blockIdx.x] = tot;
+}
+__global__ void __launch_bounds__(1024) k_enc_scan(EncodeArgs a, uint32_t nblk) {
+  __shared__ uint32_t sh16[16];
+  const uint32_t per = (nblk + 1023) / 1024, b0 = threadIdx.x * per;
+  uint32_t sum = 0;
+  for (uint32_t i = b0; i < b0 + per && i < nblk; ++i) sum += a.bsum[i];
+  uint32_t tot;
+  uint64_t run = block_excl_scan(sum, sh16, &tot);  // total bytes < 2^32 (hb_encode bounds cap)
+  for (uint32_t i = b0; i < b0 + per && i < nblk; ++i) {
+    a.bbase[i] = run;
+    run += a.bsum[i];
+  }
+  if (threadIdx.x == 0) {
+    a.bbase[nblk] = tot;
+    a.off[enc_n(a)] = tot;
+    *a.total = tot;
+  }
+}
+__global__ void __launch_bounds__(ENC_THREADS) k_enc_write(EncodeArgs a, uint32_t nblk) {
+  __shared__ uint32_t sh16[16];
+  __shared__ uint4 l_win[(ENC_THREADS / 64) * (ENC_WIN / 16)];
+  const bool write = a.bbase[nblk] <= a.bytes_cap;  // else off, status and total only
+  (void)enc_tile(a, (uint64_t)blockIdx.x * ENC_THREADS, enc_n(a), a.bbase[blockIdx.x], write, l_win, sh16);
+}
+// A batch of at most ENC_SMALL_MAX records: all three in one workgroup.
+__global__ void __launch_bounds__(ENC_SMALL_THREADS) k_enc_small(EncodeArgs a) {
+  __shared__ uint32_t sh16[16];
+  __shared__ uint4 l_win[(ENC_SMALL_THREADS / 64) * (ENC_WIN / 16)];
+  const uint64_t n = enc_n(a);
+  uint32_t sum = 0;
+  for (uint64_t i = threadIdx.x; i < n; i += ENC_SMALL_THREADS) {
+    EncRec r;
+    sum += enc_load(a, i, n, &r);
+  }
+  uint32_t tot;
+  (void)block_excl_scan(sum, sh16, &tot);
+  if (threadIdx.x == 0) {
+    a.off[n] = tot;
+    *a.total = tot;
+  }
+  const bool write = tot <= a.bytes_cap;
+  uint64_t base = 0;
+  for (uint64_t i0 = 0; i0 < n; i0 += ENC_SMALL_THREADS) base += enc_tile(a, i0, n, base, write, l_win, sh16);
+}
+
+// hb_egress: the last step's event words -> an hb_out_batch.  One workgroup
+// per partition (its P chunk, then its M chunk), one lane per group.  The
+// words of a chunk interleave the partition's groups in emission order, and a
+// record's place in the output is fixed by its word's place in the chunk: a
+// per-word "makes a record" flag (a response or a heartbeat; the engine emits
+// nothing for a group after its HB_EV_FAULT), a block scan per tile, a
+// running base per chunk, chunk bases from a scan over the chunks.  A chunk
+// goes through LDS in tiles of EG_TILE words; every lane then walks the tile's
+// group bytes (16 per LDS broadcast read) and consumes its own group's words
+// in order, carrying (term, last, pend) in registers across tiles and chunks.
+struct EgressArgs {
+  const uint64_t* ev;
+  const uint64_t* ev_off;
+  const uint32_t* ev_counts;
+  uint32_t nc, G;
+  const uint64_t *term0, *last0, *peer;
+  uint32_t* ccnt;    // [nc] records per chunk
+  uint64_t* cbase;   // [nc + 1] their exclusive scan, then the total
+  uint64_t cap;
+  uint64_t* count;
+  uint32_t *o_group, *o_info;
+  uint64_t *o_to, *o_term, *o_log_term, *o_index, *o_commit, *o_hint;
+};
+constexpr uint32_t EG_TILE = 2048;  // words of a chunk in LDS at a time (8 per lane)
+constexpr uint32_t EG_PER = EG_TILE / PART;
+constexpr uint32_t EG_SMALL = 1024;  // chunks the one-workgroup count + scan takes
+static_assert(EG_PER == 8, "a lane's group bytes of a tile are one 8-byte LDS store");
+
+__device__ __forceinline__ uint32_t eg_record(uint64_t w) {
+  const uint32_t t = (uint32_t)w & 0xF;
+  return (t == HB_EV_RESP || t == HB_EV_HEARTBEAT) ? 1u : 0u;
+}
+__global__ void __launch_bounds__(256) k_eg_count(EgressArgs a) {
+  __shared__ uint32_t sh16[16];
+  const uint32_t c = blockIdx.x, n = a.ev_counts[c];
+  const uint64_t* src = a.ev + a.ev_off[c];
+  uint32_t k = 0;
+  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) k += eg_record(src[i]);
+  uint32_t tot;
+  (void)block_excl_scan(k, sh16, &tot);
+  if (threadIdx.x == 0) a.ccnt[c] = tot;
+}
+__global__ void __launch_bounds__(1024) k_eg_scan(EgressArgs a) {
+  __shared__ uint32_t sh16[16];
+  const uint32_t n = a.nc, per = (n + 1023) / 1024, b0 = threadIdx.x * per;
+  uint32_t sum = 0;
+  for (uint32_t i = b0; i < b0 + per && i < n; ++i) sum += a.ccnt[i];
+  uint32_t tot;
+  uint64_t run = block_excl_scan(sum, sh16, &tot);  // total events < 2^32
+  for (uint32_t i = b0; i < b0 + per && i < n; ++i) {
+    a.cbase[i] = run;
+    run += a.ccnt[i];
+  }
+  if (threadIdx.x == 0) {
+    a.cbase[n] = tot;
+    *a.count = tot;
+  }
+}
+// Count and scan in one workgroup when the chunks are few: a wave per chunk counts.
+__global__ void __launch_bounds__(1024) k_eg_small(EgressArgs a) {
+  __shared__ uint32_t sh16[16];
+  __shared__ uint32_t s_cnt[EG_SMALL];
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  for (uint32_t c = wave; c < a.nc; c += 16) {
+    const uint32_t n = a.ev_counts[c];
+    const uint64_t* src = a.ev + a.ev_off[c];
+    uint32_t k = 0;
+    for (uint32_t i = lane; i < n; i += 64) k += eg_record(src[i]);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) k += __shfl_xor(k, d);
+    if (lane == 0) s_cnt[c] = k;
+  }
+  __syncthreads();
+  const uint32_t c = tid < a.nc ? s_cnt[tid] : 0u;
+  uint32_t tot;
+  const uint32_t run = block_excl_scan(c, sh16, &tot);
+  if (tid < a.nc) a.cbase[tid] = run;
+  if (tid == 0) {
+    a.cbase[a.nc] = tot;
+    *a.count = tot;
+  }
+}
+
+__global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
+  __shared__ uint64_t s_w[EG_TILE];
+  __shared__ uint32_t s_pos[EG_TILE];
+  __shared__ uint4 s_key[EG_TILE / 16];
+  __shared__ uint32_t sh16[16];
+  const uint32_t tid = threadIdx.x, part = blockIdx.x, g = part * PART + tid;
+  const bool live = g < a.G;
+  uint64_t term = live ? a.term0[g] : 0ull, last = live ? a.last0[g] : 0ull;
+  bool pend = false, dead = false;
+  const uint32_t pat = tid * 0x01010101u;
+  for (uint32_t c = 2 * part; c < 2 * part + 2; ++c) {
+    const uint32_t n = a.ev_counts[c];
+    const uint64_t* src = a.ev + a.ev_off[c];
+    uint64_t run = a.cbase[c];
+    for (uint32_t t0 = 0; t0 < n; t0 += EG_TILE) {
+      const uint32_t m = n - t0 < EG_TILE ? n - t0 : EG_TILE;
+      // stage: a lane takes EG_PER consecutive words, so one block scan places the tile's records
+      uint64_t w[EG_PER];
+      uint32_t k = 0;
+#pragma unroll
+      for (uint32_t j = 0; j < EG_PER; ++j) {
+        const uint32_t li = tid * EG_PER + j;
+        w[j] = li < m ? src[t0 + li] : (uint64_t)EVC_CONT;
+        k += eg_record(w[j]);
+      }
+      uint32_t tot;
+      uint32_t pos = block_excl_scan(k, sh16, &tot);
+      uint32_t klo = 0, khi = 0;
+#pragma unroll
+      for (uint32_t j = 0; j < EG_PER; ++j) {
+        const uint32_t li = tid * EG_PER + j;
+        s_w[li] = w[j];
+        s_pos[li] = pos;
+        pos += eg_record(w[j]);
+        const uint32_t kb = (uint32_t)(w[j] >> 16) & 0xFF;
+        if (j < 4) klo |= kb << (8 * j);
+        else khi |= kb << (8 * (j - 4));
+      }
+      reinterpret_cast<uint2*>(s_key)[tid] = make_uint2(klo, khi);
+      __syncthreads();
+      // consume: this lane's words of the tile, in order
+      const uint32_t nq = (m + 15) / 16;
+      for (uint32_t q = 0; q < nq && !dead; ++q) {
+        const uint4 kk = s_key[q];
+        const uint32_t kd[4] = {kk.x, kk.y, kk.z, kk.w};
+#pragma unroll
+        for (uint32_t d = 0; d < 4; ++d) {
+          const uint32_t x = kd[d] ^ pat;
+          if (((x - 0x01010101u) & ~x & 0x80808080u) == 0) continue;  // no byte of the four is this lane
+          for (uint32_t b = 0; b < 4; ++b) {
+            if (((x >> (8 * b)) & 0xFF) != 0 || dead) continue;
+            const uint32_t li = q * 16 + d * 4 + b;
+            if (li >= m) continue;
+            const uint64_t ww = s_w[li];
+            const uint32_t type = (uint32_t)ww & 0xF, to = (uint32_t)(ww >> 4) & 0x7F, aux = (uint32_t)(ww >> 12) & 0xF;
+            if (type == EVC_CONT) continue;  // (its group byte is 0: lane 0 meets them)
+            uint64_t xv = ww >> 24;
+            if ((ww >> 11) & 1u) {  // the continuation word follows in the chunk
+              const uint64_t cw = li + 1 < m ? s_w[li + 1] : (t0 + li + 1 < n ? src[t0 + li + 1] : 0ull);
+              xv |= (cw >> 4) << 40;
+            }
+            if (type == HB_EV_TERM) term = xv;
+            else if (type == HB_EV_LAST) last = xv;
+            else if (type == HB_EV_FOLLOW) pend |= aux == HB_FOLLOW_APPEND || aux == HB_FOLLOW_RESTORE;
+            else if (type == HB_EV_FAULT) dead = true;
+            else if (type == HB_EV_RESP || type == HB_EV_HEARTBEAT) {
+              uint32_t mtype = HB_MSG_HEARTBEAT;
+              uint64_t index = 0, commit = 0, hint = 0;
+              bool reject = false;
+              if (type == HB_EV_HEARTBEAT) {
+                commit = xv;
+              } else {
+                const uint32_t kind = aux & 7u;
+                reject = (aux & HB_RESP_REJECT) != 0;
+                mtype = kind == HB_RESP_APP ? HB_MSG_APP_RESP
+                                            : (kind == HB_RESP_HEARTBEAT ? HB_MSG_HEARTBEAT_RESP : HB_MSG_VOTE_RESP);
+                if (kind == HB_RESP_APP) {
+                  index = xv;
+                  if (reject) {
+                    hint = last;  // handleAppendEntries raft/raft.go:661-663
+                  } else if (pend) {
+                    last = xv;  // lastnewi of the append / the restored snapshot's index
+                    pend = false;
+                  }
+                }
+              }
+              const uint64_t o = run + s_pos[li];
+              if (o < a.cap) {
+                const bool slot = to <= HB_REF_SLOT_MAX;
+                a.o_group[o] = g;
+                a.o_info[o] = HB_INFO(mtype, slot ? to : (uint32_t)HB_REF_OTHER, reject);
+                a.o_to[o] = slot ? a.peer[(size_t)g * HB_PEER_ROW + to] : 0ull;
+                a.o_term[o] = term;
+                a.o_log_term[o] = 0;
+                a.o_index[o] = index;
+                a.o_commit[o] = commit;
+                a.o_hint[o] = hint;
+              }
+            }
+          }
+        }
+      }
+      __syncthreads();  // the tile is consumed
+      run += tot;
+    }
+  }
+}
+
+// The pre-step snapshot of the term and last columns (hb_set_egress).
+__global__ void __launch_bounds__(256) k_eg_snap(const uint64_t* term, const uint64_t* last, uint64_t* term0,
+                                                 uint64_t* last0, uint32_t G) {
+  const uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+  if (i + 1 < G) {
+    *reinterpret_cast<uint4*>(term0 + i) = *reinterpret_cast<const uint4*>(term + i);
+    *reinterpret_cast<uint4*>(last0 + i) = *reinterpret_cast<const uint4*>(last + i);
+  } else if (i < G) {
+    term0[i] = term[i];
+    last0[i] = last[i];
+  }
+}
+
+// ============================================================================
 // host side
 // ============================================================================
 // What one step's prep (partition + route) hands to its apply.  Two sets, so
@@ -3712,6 +4068,15 @@ struct hb_handle {
   uint64_t evx_cap = 0;
   uint64_t* evw = nullptr;        // hb_events_to_host: per-chunk word offsets + total
   uint64_t evw_cap = 0;
+  // wire egress (hb_set_egress / hb_egress / hb_encode): nothing of it exists while egress is off
+  bool egress = false;
+  bool eg_stepped = false;        // a step or tick has run since hb_set_egress(on)
+  uint64_t* term0 = nullptr;      // [G] the term column before the last step / tick
+  uint64_t* last0 = nullptr;      // [G] the last column before it
+  uint32_t* eg_cnt = nullptr;     // [2 NB] records per chunk
+  uint64_t* eg_base = nullptr;    // [2 NB + 1] their scan
+  uint32_t* enc_sum = nullptr;    // hb_encode: [blocks] bytes per pass-one workgroup (allocated on first use)
+  uint64_t* enc_base = nullptr;   // [blocks + 1]
   uint64_t* rnd = nullptr;        // the r.rand stream (hb_set_rand), grown on demand
   uint64_t rnd_cap = 0;
   // hb_move_groups scratch, grown on demand and reused (capacities in u64 words)
@@ -3862,6 +4227,22 @@ uint32_t apply_grid_for(uint32_t NBK, uint32_t sl, uint32_t NB) {
   return (need + 7) & ~7u;
 }
 uint32_t apply_grid(const hb_handle* h) { return h->agrid; }
+
+// hb_set_egress: the group's Term and lastIndex before the step (one launch, 32 B per group moved)
+void egress_snapshot(hb_handle* h, hipStream_t st) {
+  hipLaunchKernelGGL(k_eg_snap, dim3((h->G + 511) / 512), dim3(256), 0, st, (const uint64_t*)h->st.term,
+                     (const uint64_t*)h->st.last, h->term0, h->last0, h->G);
+  h->eg_stepped = true;
+}
+// A device-readable word the caller names: pinned host memory (hb_alloc_pinned) or device memory.
+template <class T>
+T* dev_view(T* p) {
+  void* d = nullptr;
+  if (p && hipHostGetDevicePointer(&d, const_cast<void*>(static_cast<const void*>(p)), 0) == hipSuccess && d)
+    return static_cast<T*>(d);
+  (void)hipGetLastError();  // not host memory: a device pointer as it is
+  return p;
+}
 
 // The apply kernels; ev = this step's phase events (HB_STEP_PROFILE) or null.
 template <uint32_t KMAX, bool X>
@@ -4154,6 +4535,9 @@ int hb_destroy(hb_handle* h) {
   if (h->peer) (void)hipFree(h->peer);
   if (h->dec_q) (void)hipFree(h->dec_q);
   if (h->dec_qn) (void)hipFree(h->dec_qn);
+  for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->eg_cnt, (void*)h->eg_base, (void*)h->enc_sum,
+                  (void*)h->enc_base})
+    if (p) (void)hipFree(p);
   if (h->in_ready) (void)hipEventDestroy(h->in_ready);
   if (h->prep) (void)hipStreamDestroy(h->prep);
   delete h;
@@ -4625,6 +5009,7 @@ int hb_tick(hb_handle* h, uint32_t flags) {
   aa.ev_off = ps.ev_off;
   aa.stats_shard = h->stats_shard;
   const uint32_t grid = apply_grid(h);
+  if (h->egress) egress_snapshot(h, st);
   switch (h->nmax) {
     case 3: hipLaunchKernelGGL(k_tick<3>, dim3(grid), dim3(PART), 0, st, aa); break;
     case 5: hipLaunchKernelGGL(k_tick<5>, dim3(grid), dim3(PART), 0, st, aa); break;
@@ -4956,6 +5341,13 @@ int hb_step(hb_handle* h, const hb_batch* b, uint32_t flags) {
   // 0.931 ms/step same box)
   const bool fused = h->nmax == 3 && !two && (h->fuse >= 2 || (h->fuse == 1 && h->passes == 1)) &&
                      PART_LOG + h->sis_log >= route_fast_rg_log(aa.kmax, xmode);
+  // Egress: the term and last columns as they are before this step, on the
+  // apply stream.  One stream: the route below is the first kernel that can
+  // write them (its storm hand-over runs the election lane).  Two stages: the
+  // route runs on the prep stream without the hand-over (aa.storm = 0) and
+  // writes no group state, so the copy is ordered after the previous step's
+  // apply and before this step's, the only writers.
+  if (h->egress) egress_snapshot(h, st);
   switch (h->nmax) {
     case 3:
       if (fused) break;
@@ -5065,6 +5457,134 @@ int hb_events_to_host(hb_handle* h, uint64_t* words, uint64_t cap, uint32_t* cou
   hipLaunchKernelGGL(k_gather_words, dim3(nc), dim3(256), 0, h->stream, (const uint64_t*)h->ev,
                      (const uint32_t*)ps.ev_counts, (const uint64_t*)ps.ev_off, (const uint64_t*)h->evw,
                      static_cast<uint64_t*>(dw), cap);
+  return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
+}
+
+// ---- wire egress ---------------------------------------------------------------
+int hb_set_egress(hb_handle* h, int on) {
+  if (!h) return HB_EINVAL;
+  DeviceGuard guard(h->device);
+  if (!on) {
+    if (!h->egress) return HB_OK;
+    HB_CHECK(hipStreamSynchronize(h->stream));  // an hb_egress may still read them
+    for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->eg_cnt, (void*)h->eg_base})
+      if (p) (void)hipFree(p);
+    h->term0 = h->last0 = h->eg_base = nullptr;
+    h->eg_cnt = nullptr;
+    h->egress = false;
+    return HB_OK;
+  }
+  if (h->egress) return HB_OK;
+  const size_t G = h->G, nc = 2 * (size_t)h->NB;
+  if (hipMalloc(&h->term0, G * 8) != hipSuccess || hipMalloc(&h->last0, G * 8) != hipSuccess ||
+      hipMalloc(&h->eg_cnt, nc * 4) != hipSuccess || hipMalloc(&h->eg_base, (nc + 1) * 8) != hipSuccess) {
+    for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->eg_cnt, (void*)h->eg_base})
+      if (p) (void)hipFree(p);
+    h->term0 = h->last0 = h->eg_base = nullptr;
+    h->eg_cnt = nullptr;
+    return HB_ENOMEM;
+  }
+  h->egress = true;
+  h->eg_stepped = false;  // the step before this call has no snapshot: its events are not replayed
+  return HB_OK;
+}
+
+int hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t cap, uint64_t* count) {
+  (void)self_id;  // m.From: hb_encode writes it; the batch holds no sender
+  if (!h || !out || !count) return HB_EINVAL;
+  if (!out->group || !out->info || !out->to || !out->term || !out->log_term || !out->index || !out->commit ||
+      !out->hint)
+    return HB_EINVAL;
+  if (!h->egress || !h->peer) return HB_EINVAL;
+  DeviceGuard guard(h->device);
+  uint64_t* dcount = dev_view(count);
+  if (!h->eg_stepped) {  // no step since hb_set_egress: no events
+    HB_CHECK(hipMemsetAsync(dcount, 0, 8, h->stream));
+    return HB_OK;
+  }
+  const PrepSet& ps = h->set[h->cur];
+  EgressArgs ea;
+  ea.ev = h->ev;
+  ea.ev_off = ps.ev_off;
+  ea.ev_counts = ps.ev_counts;
+  ea.nc = 2 * h->NB;
+  ea.G = h->G;
+  ea.term0 = h->term0;
+  ea.last0 = h->last0;
+  ea.peer = h->peer;
+  ea.ccnt = h->eg_cnt;
+  ea.cbase = h->eg_base;
+  ea.cap = cap;
+  ea.count = dcount;
+  ea.o_group = out->group;
+  ea.o_info = out->info;
+  ea.o_to = out->to;
+  ea.o_term = out->term;
+  ea.o_log_term = out->log_term;
+  ea.o_index = out->index;
+  ea.o_commit = out->commit;
+  ea.o_hint = out->hint;
+  if (ea.nc <= EG_SMALL && !h->no_small) {
+    hipLaunchKernelGGL(k_eg_small, dim3(1), dim3(1024), 0, h->stream, ea);
+  } else {
+    hipLaunchKernelGGL(k_eg_count, dim3(ea.nc), dim3(256), 0, h->stream, ea);
+    hipLaunchKernelGGL(k_eg_scan, dim3(1), dim3(1024), 0, h->stream, ea);
+  }
+  hipLaunchKernelGGL(k_egress, dim3(h->NB), dim3(PART), 0, h->stream, ea);
+  return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
+}
+
+int hb_encode(hb_handle* h, const hb_out_batch* in, uint64_t cap, const uint64_t* n_dev, uint64_t self_id,
+              uint8_t* bytes, uint64_t bytes_cap, uint64_t* off, uint8_t* status, uint64_t* total) {
+  if (!h || !in || !off || !status || !total || (bytes_cap && !bytes)) return HB_EINVAL;
+  if (!in->group || !in->info || !in->to || !in->term || !in->log_term || !in->index || !in->commit || !in->hint)
+    return HB_EINVAL;
+  const uint64_t cap_max = h->max_batch * (h->nmax + 4ull);
+  // (byte offsets inside the kernels' scans are 32-bit: 91 bytes a record at most)
+  if (cap > cap_max || cap * WO_MAX >= (1ull << 32)) return HB_EINVAL;
+  DeviceGuard guard(h->device);
+  EncodeArgs ea;
+  ea.info = in->info;
+  ea.to = in->to;
+  ea.term = in->term;
+  ea.log_term = in->log_term;
+  ea.index = in->index;
+  ea.commit = in->commit;
+  ea.hint = in->hint;
+  ea.cap = cap;
+  ea.n_dev = dev_view(n_dev);
+  ea.self_id = self_id;
+  ea.bytes = bytes;
+  ea.bytes_cap = bytes_cap;
+  ea.off = off;
+  ea.status = status;
+  ea.total = dev_view(total);
+  ea.bsum = nullptr;
+  ea.bbase = nullptr;
+  if (cap <= ENC_SMALL_MAX && !h->no_small) {
+    hipLaunchKernelGGL(k_enc_small, dim3(1), dim3(ENC_SMALL_THREADS), 0, h->stream, ea);
+    return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
+  }
+  if (!h->enc_sum) {  // once, for the largest batch the handle takes
+    const uint64_t cm = cap_max * WO_MAX >= (1ull << 32) ? ((1ull << 32) - 1) / WO_MAX : cap_max;
+    const uint64_t nb = (cm + ENC_THREADS - 1) / ENC_THREADS + 1;
+    if (hipMalloc(&h->enc_sum, nb * 4) != hipSuccess) return HB_ENOMEM;
+    if (hipMalloc(&h->enc_base, (nb + 1) * 8) != hipSuccess) {
+      (void)hipFree(h->enc_sum);
+      h->enc_sum = nullptr;
+      return HB_ENOMEM;
+    }
+  }
+  ea.bsum = h->enc_sum;
+  ea.bbase = h->enc_base;
+  const uint32_t nblk = (uint32_t)((cap + ENC_THREADS - 1) / ENC_THREADS);
+  if (nblk == 0) {  // (cap 0 with the small path off)
+    hipLaunchKernelGGL(k_enc_small, dim3(1), dim3(ENC_SMALL_THREADS), 0, h->stream, ea);
+    return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
+  }
+  hipLaunchKernelGGL(k_enc_size, dim3(nblk), dim3(ENC_THREADS), 0, h->stream, ea);
+  hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(1024), 0, h->stream, ea, nblk);
+  hipLaunchKernelGGL(k_enc_write, dim3(nblk), dim3(ENC_THREADS), 0, h->stream, ea, nblk);
   return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
 }
 

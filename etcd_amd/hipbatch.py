@@ -121,6 +121,10 @@ def lib():
         "hb_load_peers": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_void_p]),
         "hb_decode": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, P(abi.hb_batch),
                                 C.c_void_p]),
+        "hb_set_egress": (C.c_int, [H, C.c_int]),
+        "hb_egress": (C.c_int, [H, C.c_uint64, P(abi.hb_out_batch), C.c_uint64, C.c_void_p]),
+        "hb_encode": (C.c_int, [H, P(abi.hb_out_batch), C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                C.c_void_p, C.c_void_p, C.c_void_p]),
         "hb_events_device": (C.c_int, [H, P(C.c_void_p), P(C.c_void_p), P(C.c_void_p), P(C.c_uint32)]),
         "hb_copy_events": (C.c_int, [H, C.c_void_p, C.c_uint64, P(C.c_uint64)]),
         "hb_events_to_host": (C.c_int, [H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
@@ -346,6 +350,36 @@ class Engine:
         self._keep_dec = (data, off, length, group, out, status)
         _check("hb_decode", lib().hb_decode(self.h, _ptr(data), _ptr(off), _ptr(length), _ptr(group), len(off),
                                             C.byref(b), _ptr(status)))
+
+    # ---- wire egress ---------------------------------------------------------------
+    def set_egress(self, on=True):
+        """hb_set_egress: every later step / tick keeps the groups' Term and lastIndex
+        from before it, which egress() needs; off frees them."""
+        _check("hb_set_egress", lib().hb_set_egress(self.h, 1 if on else 0))
+
+    @staticmethod
+    def _out_batch(out):
+        b = abi.hb_out_batch()
+        for name, _ in abi.OUT_BATCH_FIELDS:
+            setattr(b, name, _ptr(out[name]))
+        return b
+
+    def egress(self, self_id, out, cap, count):
+        """hb_egress: the last step's payload-free outgoing messages into the device
+        tensors out = {group, info, to, term, log_term, index, commit, hint} of `cap`
+        records; count = a device (or pinned) u64 that takes the record count."""
+        b = self._out_batch(out)
+        self._keep_eg = (out, count)
+        _check("hb_egress", lib().hb_egress(self.h, self_id, C.byref(b), cap, _ptr(count)))
+
+    def encode(self, self_id, batch, cap, data, off, status, total, n_dev=None):
+        """hb_encode: the records of `batch` (an egress() out dict) as raftpb.Message bytes
+        into the device tensor `data` (u8), off [cap + 1] (u64), status [cap] (u8); total and
+        n_dev = device (or pinned) u64 words (n_dev None: cap records)."""
+        b = self._out_batch(batch)
+        self._keep_enc = (batch, data, off, status, total, n_dev)
+        _check("hb_encode", lib().hb_encode(self.h, C.byref(b), cap, _ptr(n_dev), self_id, _ptr(data),
+                                            0 if data is None else len(data), _ptr(off), _ptr(status), _ptr(total)))
 
     def step_batch(self, batch, **kw):
         return self.step(batch["group"], batch["info"], batch["term"], batch["index"],

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define HB_ABI_VERSION 6
+#define HB_ABI_VERSION 7
 
 /* ---- error codes -------------------------------------------------------- */
 #define HB_OK          0
@@ -535,6 +535,60 @@ int  hb_tick(hb_handle* h, uint32_t flags);
 int  hb_load_peers(hb_handle* h, uint32_t first, uint32_t count, const uint64_t* ids);
 int  hb_decode(hb_handle* h, const uint8_t* bytes, const uint64_t* off, const uint32_t* len,
                const uint32_t* group, uint64_t n, const hb_batch* out, uint8_t* status);
+
+/* ---- wire egress ---------------------------------------------------------
+ * The send path's counterpart of hb_decode: the payload-free messages a step
+ * or tick produces (MsgAppResp, MsgHeartbeatResp, MsgVoteResp, MsgHeartbeat:
+ * no entries, the empty snapshot) leave the device as the bytes
+ * Message.MarshalTo writes (raft/raftpb/raft.pb.go:1271-1330), ready for the
+ * transport, without the host replaying an event.  Two calls, both
+ * asynchronous on the handle's stream:
+ *   hb_egress  the last step's events -> a batch of outgoing messages
+ *   hb_encode  such a batch -> wire bytes
+ * A batch is a structure of arrays in device memory, capacity `cap` records: */
+typedef struct hb_out_batch {
+  uint32_t* group;    /* group slot                                                   */
+  uint32_t* info;     /* HB_INFO(type, to_ref, reject); to_ref = slot or HB_REF_OTHER */
+  uint64_t* to;       /* m.To as a node id (0 when to_ref == HB_REF_OTHER)            */
+  uint64_t* term;     /* m.Term */
+  uint64_t* log_term; /* m.LogTerm */
+  uint64_t* index;    /* m.Index */
+  uint64_t* commit;   /* m.Commit */
+  uint64_t* hint;     /* m.RejectHint */
+} hb_out_batch;
+/* Egress on: every later hb_step / hb_tick first copies the groups' Term and
+ * lastIndex columns (16 B per group, allocated here) so that hb_egress can
+ * give each message the Term and each rejection the RejectHint of the point
+ * of its send: the events are a delta, the state after the step holds only
+ * the final values.  Off (the default): nothing is allocated, copied or
+ * launched, and hb_egress returns HB_EINVAL. */
+int  hb_set_egress(hb_handle* h, int on);
+/* One record per HB_EV_RESP / HB_EV_HEARTBEAT event of the last step or tick
+ * (since hb_set_egress), in chunk order then word order of hb_events_device:
+ * a group's records are in the order the reference appended the messages to
+ * r.msgs.  m.Term = the group's Term at the send; a rejecting MsgAppResp's
+ * RejectHint = its lastIndex at the send; `to` = the node id hb_load_peers
+ * gave the slot (HB_EINVAL if no peer row was ever loaded), or to_ref =
+ * HB_REF_OTHER and to = 0 for a sender outside prs (the host knows its id).
+ * Messages with entries, a snapshot or a LogTerm (HB_EV_APP / _SNAP / _VOTE,
+ * HB_EV_PROP_FWD) make no record: the host builds them as before.  self_id
+ * is this node's id; a record holds no sender (hb_encode writes m.From), so
+ * hb_egress only takes it for symmetry with hb_encode.
+ * *count (device-readable: device memory or hb_alloc_pinned memory) = the
+ * number of records; when it exceeds cap only the first cap are written and
+ * the caller calls again (the events stay valid until the next step). */
+int  hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t cap, uint64_t* count);
+/* Record i (m.From = self_id) becomes bytes[off[i], off[i+1]), packed densely
+ * in record order, 28 to 91 bytes each; off[n] and *total = the byte count.
+ * n = *n_dev (device-readable like *total, e.g. hb_egress's count, clamped to
+ * cap; NULL = cap).  status[i] = HB_WIRE_OK, or HB_WIRE_HOST with length 0 for
+ * a record whose to_ref is HB_REF_OTHER.  When *total > bytes_cap no byte is
+ * written (off, status and total are): call again with a larger buffer, 91 x n
+ * always suffices.  HB_EINVAL before any device work: a NULL handle or array,
+ * cap > max_batch x (max_replicas + 4), cap x 91 >= 2^32. */
+int  hb_encode(hb_handle* h, const hb_out_batch* in, uint64_t cap, const uint64_t* n_dev, uint64_t self_id,
+               uint8_t* bytes, uint64_t bytes_cap, uint64_t* off /* [cap + 1] */, uint8_t* status /* [cap] */,
+               uint64_t* total);
 
 /* ---- the hot path ----------------------------------------------------------
  * Step one batch (all messages of the batch, per group in arrival order).

@@ -1,0 +1,88 @@
+"""The replay rules of wire egress, restated in Python.
+
+replay() turns a step's events (hb_event records, the engine's or the
+oracle's) into the payload-free messages the reference appended to r.msgs:
+MsgAppResp, MsgHeartbeatResp, MsgVoteResp and MsgHeartbeat.  A message's Term
+and a rejection's RejectHint are the group's Term and lastIndex at the point
+of the send, so every group is replayed from its record before the step.
+tests/test_egress_replay.py pins these rules to the oracle's own r.msgs;
+tests/test_egress_gpu.py uses them as the reference of hb_egress.
+"""
+import numpy as np
+
+from etcd_amd import abi
+
+EGRESS_TYPES = (abi.HB_MSG_APP_RESP, abi.HB_MSG_HEARTBEAT_RESP, abi.HB_MSG_VOTE_RESP, abi.HB_MSG_HEARTBEAT)
+FIELDS = ("group", "type", "to_ref", "to", "frm", "term", "log_term", "index", "commit", "reject", "hint")
+
+
+def replay(events, groups0, peers, self_id):
+    """events: EVENT_DTYPE records (a group's in order); groups0: GROUP_DTYPE records
+    before the step; peers: [G, HB_MAX_REPLICAS] node ids.  Returns the messages as
+    tuples of FIELDS, in event order."""
+    state = {}
+    out = []
+    for e in events:
+        g = int(e["group"])
+        s = state.get(g)
+        if s is None:
+            s = state[g] = [int(groups0[g]["term"]), int(groups0[g]["last_index"]), False, False]
+        if s[3]:  # faulted: the replay ended
+            continue
+        t, to, aux, x = int(e["type"]), int(e["to"]), int(e["aux"]), int(e["x"])
+        if t == abi.HB_EV_TERM:
+            s[0] = x
+        elif t == abi.HB_EV_LAST:
+            s[1] = x
+        elif t == abi.HB_EV_FOLLOW:
+            if aux in (abi.HB_FOLLOW_APPEND, abi.HB_FOLLOW_RESTORE):
+                s[2] = True
+        elif t == abi.HB_EV_FAULT:
+            s[3] = True
+        elif t in (abi.HB_EV_RESP, abi.HB_EV_HEARTBEAT):
+            slot = to <= abi.HB_REF_SLOT_MAX
+            to_ref = to if slot else abi.HB_REF_OTHER
+            to_id = int(peers[g][to]) if slot else 0
+            mtype, index, commit, reject, hint = abi.HB_MSG_HEARTBEAT, 0, 0, False, 0
+            if t == abi.HB_EV_HEARTBEAT:
+                commit = x
+            else:
+                kind = aux & 7
+                reject = bool(aux & abi.HB_RESP_REJECT)
+                mtype = {abi.HB_RESP_APP: abi.HB_MSG_APP_RESP, abi.HB_RESP_HEARTBEAT: abi.HB_MSG_HEARTBEAT_RESP,
+                         abi.HB_RESP_VOTE: abi.HB_MSG_VOTE_RESP}[kind]
+                if kind == abi.HB_RESP_APP:
+                    index = x
+                    if reject:
+                        hint = s[1]
+                    elif s[2]:
+                        s[1], s[2] = x, False
+            out.append((g, mtype, to_ref, to_id, self_id, s[0], 0, index, commit, reject, hint))
+    return out
+
+
+def by_group(records):
+    """Stable sort by group: the only order the engine promises across groups."""
+    return sorted(records, key=lambda r: r[0])
+
+
+def marshal(rec):
+    """The wire bytes of one replayed record (b'' for HB_REF_OTHER: the host sends it)."""
+    from .wire_util import gogo_marshal
+    g, mtype, to_ref, to, frm, term, log_term, index, commit, reject, hint = rec
+    if to_ref == abi.HB_REF_OTHER:
+        return b""
+    return gogo_marshal(mtype, to=to, frm=frm, term=term, log_term=log_term, index=index, commit=commit,
+                        reject=reject, hint=hint)
+
+
+def out_arrays(records):
+    """The hb_out_batch arrays of a list of records (numpy, abi.OUT_BATCH_FIELDS)."""
+    n = len(records)
+    a = {name: np.zeros(n, dtype=dt) for name, dt in abi.OUT_BATCH_FIELDS}
+    for i, (g, mtype, to_ref, to, frm, term, log_term, index, commit, reject, hint) in enumerate(records):
+        a["group"][i] = g
+        a["info"][i] = abi.hb_info(mtype, to_ref, reject)
+        a["to"][i], a["term"][i], a["log_term"][i] = to, term, log_term
+        a["index"][i], a["commit"][i], a["hint"][i] = index, commit, hint
+    return a

@@ -1,0 +1,196 @@
+#!/usr/bin/env python3
+"""Micro-benchmark of wire egress: hb_egress + hb_encode (not product code).
+
+Two workloads on a handle of 1,048,576 groups x 3:
+
+  follow  the follow workload of bench.py (synth.follow_groups / follow_batch:
+          every group receives its leader's MsgApp and MsgHeartbeat), so a step
+          leaves one MsgAppResp and one MsgHeartbeatResp per group to send;
+  tick    one MultiNode.Tick with half the groups leaders beating
+          (HeartbeatTick 1): two MsgHeartbeat per leader.
+
+Per workload: the step (or tick) runs once with egress on, then hb_egress +
+hb_encode (chained through the device-resident count, no host sync between
+them) run 3 warm-up and 25 timed times over that step's events, each pair
+bracketed by HIP events on the handle's stream.  Reported: median [min, max]
+in microseconds, the records and wire bytes, and the bytes of a model with the
+rate it implies at the median:
+
+  events read (8 B per word) + the snapshot (16 B per group) + the peer id
+  (8 B per record) + the record written and read back (56 + 52 B) + the wire
+  bytes written.
+
+(The model counts the event words once; hb_egress's count pass reads them a
+second time.)  The cost of the pre-step snapshot is measured beside it: K
+back-to-back steps of the follow and the cfg2 workload with egress off and on.
+
+  python tools/microbench/egress_bench.py [--out profiles/egress_bench.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+
+from etcd_amd import abi, synth  # noqa: E402
+from etcd_amd.hipbatch import Engine  # noqa: E402
+
+G, N, W, SELF = 1 << 20, 3, 256, 1
+REC_WRITE, REC_READ = 2 * 4 + 6 * 8, 4 + 6 * 8
+
+
+def dv(torch, a):
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy(a.view({4: np.int32, 8: np.int64, 1: np.uint8}[a.dtype.itemsize])).cuda()
+
+
+def peers():
+    p = np.zeros((G, abi.HB_MAX_REPLICAS), np.uint64)
+    p[:, :N] = np.arange(1, N + 1, dtype=np.uint64)
+    return p
+
+
+class Sink:
+    """Device buffers of one hb_egress + hb_encode pair."""
+
+    def __init__(self, torch, cap):
+        self.cap = cap
+        self.out = {name: torch.zeros(cap, dtype=torch.int32 if dt == "<u4" else torch.int64, device="cuda")
+                    for name, dt in abi.OUT_BATCH_FIELDS}
+        self.count = torch.zeros(1, dtype=torch.int64, device="cuda")
+        self.total = torch.zeros(1, dtype=torch.int64, device="cuda")
+        self.data = torch.zeros(91 * cap, dtype=torch.uint8, device="cuda")
+        self.off = torch.zeros(cap + 1, dtype=torch.int64, device="cuda")
+        self.status = torch.zeros(cap, dtype=torch.uint8, device="cuda")
+
+    def run(self, eng):
+        eng.egress(SELF, self.out, self.cap, self.count)
+        eng.encode(SELF, self.out, self.cap, self.data, self.off, self.status, self.total, n_dev=self.count)
+
+
+def timed(torch, stream, eng, sink, reps):
+    us = []
+    for rep in range(3 + reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        sink.run(eng)
+        e1.record(stream)
+        e1.synchronize()
+        if rep >= 3:
+            us.append(e0.elapsed_time(e1) * 1e3)
+    return us
+
+
+def report(name, eng, sink, us, reps):
+    _, counts = eng.event_words()
+    words = int(counts.sum())
+    records, wire = int(sink.count.item()), int(sink.total.item())
+    model = 8 * words + 16 * G + 8 * records + (REC_WRITE + REC_READ) * records + wire
+    r = dict(case=name, groups=G, replicas=N, reps=reps, event_words=words, records=records, wire_bytes=wire,
+             event_us=dict(median=float(np.median(us)), min=float(np.min(us)), max=float(np.max(us))),
+             model_bytes=int(model), model_GBps_at_median=float(model / np.median(us) / 1e3),
+             records_per_s_at_median=float(records / np.median(us) * 1e6))
+    print(json.dumps(r), flush=True)
+    return r
+
+
+def steps_ms(torch, stream, one, steps, warmup=5):
+    for k in range(warmup):
+        one(k)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(stream)
+    for k in range(warmup, warmup + steps):
+        one(k)
+    e1.record(stream)
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--reps", type=int, default=25)
+    ap.add_argument("--steps", type=int, default=20)
+    args = ap.parse_args()
+    import torch
+    stream = torch.cuda.Stream()
+    results, snapshot = [], []
+    with torch.cuda.stream(stream):
+        # ---- follow ---------------------------------------------------------------------
+        seed = 0x5EED0006
+        g, _ = synth.follow_groups(G, N, seed=seed, with_runs=False)
+        b = synth.follow_batch(g, 0, seed=seed)
+        nmsg = len(b["group"])
+        eng = Engine(G, max_replicas=N, max_inflight=W, max_batch=nmsg, stream=stream)
+        eng.load_groups(g)
+        eng.load_peers(peers())
+        d = {k: dv(torch, b[k]) for k in ("group", "info", "term", "hint", "eoff", "eterm", "index", "commit")}
+        i_inc = dv(torch, ((b["info"] & 0xF) == abi.HB_MSG_APP).astype(np.uint64))
+        total_steps = 2 * (5 + args.steps) + 1
+
+        def follow(k):
+            eng.step(d["group"], d["info"], d["term"], d["index"] + i_inc * k, d["hint"], None, host=False,
+                     eoff=d["eoff"], commit=d["commit"] + k, eterm=d["eterm"])
+        off_ms = steps_ms(torch, stream, follow, args.steps)
+        eng.set_egress(True)
+        on_ms = steps_ms(torch, stream, lambda k: follow(5 + args.steps + k), args.steps)
+        snapshot.append(dict(workload="follow", steps=args.steps, ms_per_step_egress_off=off_ms,
+                             ms_per_step_egress_on=on_ms))
+        follow(total_steps - 1)
+        sink = Sink(torch, nmsg)
+        us = timed(torch, stream, eng, sink, args.reps)
+        results.append(report("follow: MsgAppResp + MsgHeartbeatResp per group", eng, sink, us, args.reps))
+        assert int(sink.count.item()) == nmsg and (sink.status.cpu().numpy() == abi.HB_WIRE_OK).all()
+        eng.close()
+        del sink
+        # ---- cfg2 steps, egress off / on (the snapshot's cost on the headline step) -----
+        seed = 0x5EED0002
+        g, _ = synth.steady_groups(G, N, seed=seed, with_runs=False)
+        eng = Engine(G, max_replicas=N, max_inflight=W, max_batch=2 * G, stream=stream)
+        eng.load_groups(g)
+        b0 = synth.cfg2_batch(g, 0, seed=seed)  # step k acks last + k + 1 (the same arrival order every step)
+        x = {k: dv(torch, b0[k]) for k in ("group", "info", "term", "index", "props")}
+
+        def cfg2(k):
+            eng.step(x["group"], x["info"], x["term"], x["index"] + k, None, x["props"], host=False)
+        off_ms = steps_ms(torch, stream, cfg2, args.steps)
+        eng.set_egress(True)
+        on_ms = steps_ms(torch, stream, lambda k: cfg2(5 + args.steps + k), args.steps)
+        snapshot.append(dict(workload="cfg2", steps=args.steps, ms_per_step_egress_off=off_ms,
+                             ms_per_step_egress_on=on_ms))
+        print(json.dumps(snapshot), flush=True)
+        eng.close()
+        del x
+        # ---- tick: half the groups leaders beating ------------------------------------
+        g, _ = synth.steady_groups(G, N, seed=seed, with_runs=False)
+        g["state"][1::2] = abi.HB_STATE_FOLLOWER
+        g["lead"][1::2] = 1
+        eng = Engine(G, max_replicas=N, max_inflight=W, max_batch=G, stream=stream)  # (hb_encode: cap <= max_batch x (n + 4))
+        eng.load_groups(g)
+        eng.load_peers(peers())
+        t = synth.random_timers(G, seed=seed, et_hi=10, ht_hi=1, pos_hi=0)
+        t["election_tick"] = 10
+        t["elapsed"] = 0
+        eng.load_timers(t)
+        eng.set_rand(np.random.default_rng(seed).integers(0, 1 << 63, 64, dtype=np.uint64))
+        eng.set_egress(True)
+        eng.tick()
+        sink = Sink(torch, 2 * G)
+        us = timed(torch, stream, eng, sink, args.reps)
+        results.append(report("tick: half the groups leaders, two MsgHeartbeat each", eng, sink, us, args.reps))
+        assert int(sink.count.item()) == (N - 1) * (G // 2)
+        eng.close()
+    out = dict(bench="hb_egress + hb_encode", results=results, snapshot_cost=snapshot)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
