@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-HB_ABI_VERSION = 7
+HB_ABI_VERSION = 8
 
 HB_OK = 0
 HB_EINVAL = -1
@@ -18,6 +18,7 @@ HB_EINVARIANT = -4
 
 HB_MAX_REPLICAS = 7
 HB_MAX_INFLIGHT = 1024
+HB_EGRESS_MAX_PEERS = 255
 HB_NO_LIMIT = (1 << 64) - 1
 HB_NO_INDEX = (1 << 64) - 1
 HB_SIZE_RING_MIN = 16

@@ -29,6 +29,7 @@
 #include "hipbatch_lead.h"
 #include "hipbatch_wire.h"
 #include "hipbatch_wire_out.h"
+#include "hipbatch_bin.h"
 
 using namespace hb;
 
@@ -3909,6 +3910,374 @@ __global__ void __launch_bounds__(256) k_eg_snap(const uint64_t* term, const uin
 }
 
 // ============================================================================
+// Per-peer egress: hb_egress_bin, hb_peer_spans
+// ============================================================================
+// A stable multi-split of an hb_out_batch by destination node: at most 256
+// bins (the node table of hb_set_egress_peers and "other"), the records of a
+// bin in the order they had in the input.  Tiles of BIN_TILE records: a
+// histogram pass classifies every record (hipbatch_bin.h, the table in LDS),
+// keeps its bin as a key byte and counts the tile's bins; a workgroup per bin
+// scans the bin's counts over the tiles; the scatter ranks a tile stably from
+// the key bytes (the partition's in-wave ranking: 8 ballots per 64-record
+// round, per-wave counters across the waves), stages it in LDS in bin order and
+// writes each bin's run of every array contiguously; its first workgroup writes
+// bin_off.  A batch of at most ENC_SMALL_MAX records does all of it in one
+// workgroup, its key bytes in LDS, and stores from registers.
+struct BinArgs {
+  const uint32_t *i_group, *i_info;
+  const uint64_t *i_to, *i_term, *i_log_term, *i_index, *i_commit, *i_hint;
+  uint32_t *o_group, *o_info;
+  uint64_t *o_to, *o_term, *o_log_term, *o_index, *o_commit, *o_hint;
+  uint32_t* src;          // null: not wanted
+  uint64_t* bin_off;      // [np + 2]
+  const BinTable* table;  // device copy, ids ascending
+  uint32_t np;            // ids in the table; bin np = "other"
+  uint32_t cap;
+  const uint64_t* n_dev;  // null: cap
+  uint8_t* key;           // [cap] the bin of every record (tiled path)
+  uint32_t* hist;         // [np + 1][ntiles] counts, then each bin's exclusive scan (tiled path)
+  uint32_t* tot;          // [np + 1] records per bin
+  uint32_t ntiles;
+};
+constexpr uint32_t BIN_THREADS = 1024;
+constexpr uint32_t BIN_WAVES = BIN_THREADS / 64;
+constexpr uint32_t BIN_ROUNDS = 2;
+constexpr uint32_t BIN_TILE = BIN_THREADS * BIN_ROUNDS;  // 2048, as the partition's
+static_assert(BIN_SLOTS == 256 && BIN_WAVES * BIN_SLOTS % BIN_THREADS == 0, "a key is one byte");
+
+__device__ __forceinline__ uint32_t bin_n(const BinArgs& a) {
+  const uint64_t n = a.n_dev ? *a.n_dev : (uint64_t)a.cap;
+  return n < a.cap ? (uint32_t)n : a.cap;
+}
+__device__ __forceinline__ void bin_table_load(const BinArgs& a, uint64_t* s_id, uint8_t* s_bin) {
+  for (uint32_t i = threadIdx.x; i < a.np; i += blockDim.x) {
+    s_id[i] = a.table->id[i];
+    s_bin[i] = a.table->bin[i];
+  }
+}
+// Stable destinations of one tile.  Record (wave, r, lane) of the tile is its
+// record wave * 128 + r * 64 + lane, so (wave, round, lane) order is input order.
+// s_off[b] = the first output record of the tile's bin b on entry, the one
+// after its last on return; s_cnt[b] (optional) = the tile's records of bin b.
+// All threads call it; it ends on a barrier.
+__device__ __forceinline__ void bin_rank_tile(const uint32_t (&key)[BIN_ROUNDS], const bool (&valid)[BIN_ROUNDS],
+                                              uint32_t (*s_wcnt)[BIN_SLOTS], uint32_t* s_off,
+                                              uint32_t (&dest)[BIN_ROUNDS], uint32_t* s_cnt = nullptr) {
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+#pragma unroll
+  for (uint32_t k = 0; k < BIN_WAVES * BIN_SLOTS / BIN_THREADS; ++k) (&s_wcnt[0][0])[tid + k * BIN_THREADS] = 0;
+  __syncthreads();
+  uint32_t vr[BIN_ROUNDS];
+#pragma unroll
+  for (uint32_t r = 0; r < BIN_ROUNDS; ++r) {
+    uint64_t peers = __ballot(valid[r]);
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k) {
+      const bool bit = (key[r] >> k) & 1u;
+      const uint64_t bk = __ballot(bit);
+      peers &= bit ? bk : ~bk;
+    }
+    const uint32_t rank = (uint32_t)__popcll(peers & lt);
+    const uint32_t before = valid[r] ? s_wcnt[wave][key[r]] : 0u;
+    vr[r] = before + rank;
+    if (valid[r] && rank == 0) s_wcnt[wave][key[r]] = before + (uint32_t)__popcll(peers);
+  }
+  __syncthreads();
+  if (tid < BIN_SLOTS) {  // per bin: prefix over the waves from the bin's start
+    uint32_t run = s_off[tid];
+#pragma unroll
+    for (uint32_t w = 0; w < BIN_WAVES; ++w) {
+      const uint32_t c = s_wcnt[w][tid];
+      s_wcnt[w][tid] = run;
+      run += c;
+    }
+    if (s_cnt) s_cnt[tid] = run - s_off[tid];
+    s_off[tid] = run;
+  }
+  __syncthreads();
+#pragma unroll
+  for (uint32_t r = 0; r < BIN_ROUNDS; ++r) dest[r] = valid[r] ? s_wcnt[wave][key[r]] + vr[r] : 0u;
+  __syncthreads();  // the counters are free for the next tile
+}
+struct BinRec {
+  uint32_t group, info;
+  uint64_t to, term, log_term, index, commit, hint;
+};
+__device__ __forceinline__ void bin_rec_load(const BinArgs& a, uint32_t i, BinRec* r) {
+  r->group = a.i_group[i];
+  r->info = a.i_info[i];
+  r->to = a.i_to[i];
+  r->term = a.i_term[i];
+  r->log_term = a.i_log_term[i];
+  r->index = a.i_index[i];
+  r->commit = a.i_commit[i];
+  r->hint = a.i_hint[i];
+}
+// record i of the input becomes record d of the output (d < n: the scan of n records' counts)
+__device__ __forceinline__ void bin_rec_store(const BinArgs& a, uint32_t d, uint32_t i, uint32_t n, const BinRec& r) {
+  if (d >= n) return;
+  a.o_group[d] = r.group;
+  a.o_info[d] = r.info;
+  a.o_to[d] = r.to;
+  a.o_term[d] = r.term;
+  a.o_log_term[d] = r.log_term;
+  a.o_index[d] = r.index;
+  a.o_commit[d] = r.commit;
+  a.o_hint[d] = r.hint;
+  if (a.src) a.src[d] = i;
+}
+
+__global__ void __launch_bounds__(BIN_THREADS) k_bin_hist(BinArgs a) {
+  __shared__ uint64_t s_id[BIN_SLOTS];
+  __shared__ uint8_t s_bin[BIN_SLOTS];
+  __shared__ uint32_t s_cnt[BIN_SLOTS];
+  const uint32_t tid = threadIdx.x, n = bin_n(a), i0 = blockIdx.x * BIN_TILE;
+  uint32_t info[BIN_ROUNDS];
+  uint64_t to[BIN_ROUNDS];
+#pragma unroll
+  for (uint32_t r = 0; r < BIN_ROUNDS; ++r) {
+    const uint32_t i = i0 + r * BIN_THREADS + tid;
+    info[r] = i < n ? a.i_info[i] : 0u;
+    to[r] = i < n ? a.i_to[i] : 0ull;
+  }
+  bin_table_load(a, s_id, s_bin);
+  if (tid < BIN_SLOTS) s_cnt[tid] = 0;
+  __syncthreads();
+#pragma unroll
+  for (uint32_t r = 0; r < BIN_ROUNDS; ++r) {
+    const uint32_t i = i0 + r * BIN_THREADS + tid;
+    if (i < n) {
+      const uint32_t b = bin_of(s_id, s_bin, a.np, info[r], to[r]);
+      a.key[i] = (uint8_t)b;
+      atomicAdd(&s_cnt[b], 1u);
+    }
+  }
+  __syncthreads();
+  if (tid <= a.np) a.hist[(size_t)tid * a.ntiles + blockIdx.x] = s_cnt[tid];
+}
+// Workgroup b turns bin b's counts of every tile into exclusive per-tile prefixes
+// (SCAN_PER tiles per lane per chunk) and writes their total to tot[b], as k_scan_rows.
+__global__ void __launch_bounds__(1024) k_bin_scan(BinArgs a) {
+  __shared__ uint32_t sh16[16];
+  uint32_t* row = a.hist + (size_t)blockIdx.x * a.ntiles;
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < a.ntiles; base += 1024 * SCAN_PER) {
+    const uint32_t i0 = base + threadIdx.x * SCAN_PER;
+    uint32_t v[SCAN_PER], sum = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < SCAN_PER; ++k) {
+      v[k] = i0 + k < a.ntiles ? row[i0 + k] : 0u;
+      sum += v[k];
+    }
+    uint32_t tot;
+    uint32_t run = carry + block_excl_scan(sum, sh16, &tot);
+#pragma unroll
+    for (uint32_t k = 0; k < SCAN_PER; ++k) {
+      if (i0 + k < a.ntiles) row[i0 + k] = run;
+      run += v[k];
+    }
+    carry += tot;
+  }
+  if (threadIdx.x == 0) a.tot[blockIdx.x] = carry;
+}
+// Two u64 columns of the tile through LDS: in at the records' places in bin
+// order (p), out at this thread's output places j = r * BIN_THREADS + tid.
+__device__ __forceinline__ void bin_stage_swap(uint64_t* st0, uint64_t* st1, const uint32_t (&p)[BIN_ROUNDS],
+                                               const bool (&valid)[BIN_ROUNDS], const bool (&ov)[BIN_ROUNDS],
+                                               uint64_t (&x)[BIN_ROUNDS], uint64_t (&y)[BIN_ROUNDS]) {
+#pragma unroll
+  for (uint32_t r = 0; r < BIN_ROUNDS; ++r)
+    if (valid[r]) {
+      st0[p[r]] = x[r];
+      st1[p[r]] = y[r];
+    }
+  __syncthreads();
+#pragma unroll
+  for (uint32_t r = 0; r < BIN_ROUNDS; ++r)
+    if (ov[r]) {
+      x[r] = st0[r * BIN_THREADS + threadIdx.x];
+      y[r] = st1[r * BIN_THREADS + threadIdx.x];
+    }
+  __syncthreads();
+}
+// block_excl_scan of two values at once (one set of barriers): v0's exclusive
+// prefix is returned with its total, v1's goes to *e1 with its total.
+__device__ __forceinline__ uint32_t block_excl_scan2(uint32_t v0, uint32_t v1, uint32_t (*sh)[16], uint32_t* t0,
+                                                     uint32_t* e1, uint32_t* t1) {
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const uint32_t i0 = wave_incl_scan(v0), i1 = wave_incl_scan(v1);
+  if (lane == 63) {
+    sh[0][wave] = i0;
+    sh[1][wave] = i1;
+  }
+  __syncthreads();
+  if (wave == 0) {
+    uint32_t x0 = lane < nw ? sh[0][lane] : 0, x1 = lane < nw ? sh[1][lane] : 0;
+    x0 = wave_incl_scan(x0);
+    x1 = wave_incl_scan(x1);
+    if (lane < nw) {
+      sh[0][lane] = x0;
+      sh[1][lane] = x1;
+    }
+  }
+  __syncthreads();
+  const uint32_t b0 = wave == 0 ? 0 : sh[0][wave - 1], b1 = wave == 0 ? 0 : sh[1][wave - 1];
+  *t0 = sh[0][nw - 1];
+  *t1 = sh[1][nw - 1];
+  __syncthreads();
+  *e1 = b1 + i1 - v1;
+  return b0 + i0 - v0;
+}
+// A bin's base is the scan of the bins' totals: every workgroup scans the 256
+// words itself, as the radix scatter does, in the barriers of the scan of its
+// own tile's counts, and the first one writes bin_off.  The tile goes through
+// LDS in bin order, two u64 columns at a time, so that a bin's records of the
+// tile leave as one contiguous run per array: storing each record from the
+// registers that loaded it cost 1.9 x the kernel at 65 bins and the same at 4
+// (DESIGN.md §3.16).
+__global__ void __launch_bounds__(BIN_THREADS) k_bin_scatter(BinArgs a) {
+  __shared__ uint32_t s_wcnt[BIN_WAVES][BIN_SLOTS];
+  __shared__ uint32_t s_off[BIN_SLOTS], s_cnt[BIN_SLOTS], s_dstart[BIN_SLOTS], s_gstart[BIN_SLOTS], sh32[2][16];
+  __shared__ uint8_t s_skey[BIN_TILE];
+  __shared__ uint64_t st0[BIN_TILE], st1[BIN_TILE];
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n = bin_n(a);
+  uint32_t key[BIN_ROUNDS], dest[BIN_ROUNDS], idx[BIN_ROUNDS];
+  bool valid[BIN_ROUNDS];
+  BinRec rec[BIN_ROUNDS] = {};
+#pragma unroll
+  for (uint32_t r = 0; r < BIN_ROUNDS; ++r) {
+    idx[r] = blockIdx.x * BIN_TILE + wave * (64 * BIN_ROUNDS) + r * 64 + lane;
+    valid[r] = idx[r] < n;
+    key[r] = valid[r] ? (uint32_t)a.key[idx[r]] : 0u;
+    if (valid[r]) bin_rec_load(a, idx[r], &rec[r]);
+  }
+  const uint32_t btot = tid <= a.np ? a.tot[tid] : 0u;  // (crosses the ranking in flight)
+  // s_off: the tile's place inside each bin; dest then counts from the bin's first record
+  if (tid < BIN_SLOTS) s_off[tid] = tid <= a.np ? a.hist[(size_t)tid * a.ntiles + blockIdx.x] : 0u;
+  bin_rank_tile(key, valid, s_wcnt, s_off, dest, s_cnt);  // (its first barrier orders s_off)
+  {
+    uint32_t m, base, all;  // the tile's records; this lane's bin's base; the batch's records
+    const uint32_t excl = block_excl_scan2(tid < BIN_SLOTS ? s_cnt[tid] : 0u, btot, sh32, &m, &base, &all);
+    if (tid < BIN_SLOTS) {
+      s_dstart[tid] = excl;                               // the bin's first place in the staged tile
+      s_gstart[tid] = base + (s_off[tid] - s_cnt[tid]);   // ... and in the output
+    }
+    if (blockIdx.x == 0) {
+      if (tid <= a.np) a.bin_off[tid] = base;
+      if (tid == 0) a.bin_off[a.np + 1] = all;
+    }
+    __syncthreads();
+    uint32_t p[BIN_ROUNDS], od[BIN_ROUNDS];
+    bool ov[BIN_ROUNDS];
+#pragma unroll
+    for (uint32_t r = 0; r < BIN_ROUNDS; ++r) {
+      p[r] = 0;
+      if (valid[r]) {  // (s_off[b] is now the end of the tile's run inside bin b)
+        p[r] = s_dstart[key[r]] + (dest[r] - (s_off[key[r]] - s_cnt[key[r]]));
+        s_skey[p[r]] = (uint8_t)key[r];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t r = 0; r < BIN_ROUNDS; ++r) {
+      const uint32_t j = r * BIN_THREADS + tid;
+      ov[r] = j < m;
+      const uint32_t b = ov[r] ? (uint32_t)s_skey[j] : 0u;
+      od[r] = s_gstart[b] + (j - s_dstart[b]);
+    }
+    uint64_t x[BIN_ROUNDS], y[BIN_ROUNDS];
+#pragma unroll
+    for (uint32_t r = 0; r < BIN_ROUNDS; ++r) {
+      x[r] = (uint64_t)rec[r].group | ((uint64_t)rec[r].info << 32);
+      y[r] = idx[r];
+    }
+    bin_stage_swap(st0, st1, p, valid, ov, x, y);
+#pragma unroll
+    for (uint32_t r = 0; r < BIN_ROUNDS; ++r) {
+      rec[r].group = (uint32_t)x[r];
+      rec[r].info = (uint32_t)(x[r] >> 32);
+      idx[r] = (uint32_t)y[r];
+      x[r] = rec[r].to;
+      y[r] = rec[r].term;
+    }
+    bin_stage_swap(st0, st1, p, valid, ov, x, y);
+#pragma unroll
+    for (uint32_t r = 0; r < BIN_ROUNDS; ++r) {
+      rec[r].to = x[r];
+      rec[r].term = y[r];
+      x[r] = rec[r].log_term;
+      y[r] = rec[r].index;
+    }
+    bin_stage_swap(st0, st1, p, valid, ov, x, y);
+#pragma unroll
+    for (uint32_t r = 0; r < BIN_ROUNDS; ++r) {
+      rec[r].log_term = x[r];
+      rec[r].index = y[r];
+      x[r] = rec[r].commit;
+      y[r] = rec[r].hint;
+    }
+    bin_stage_swap(st0, st1, p, valid, ov, x, y);
+#pragma unroll
+    for (uint32_t r = 0; r < BIN_ROUNDS; ++r) {
+      rec[r].commit = x[r];
+      rec[r].hint = y[r];
+      if (ov[r]) bin_rec_store(a, od[r], idx[r], n, rec[r]);
+    }
+  }
+}
+// A batch of at most ENC_SMALL_MAX records: classify, scan and scatter in one workgroup.
+__global__ void __launch_bounds__(BIN_THREADS) k_bin_small(BinArgs a) {
+  __shared__ uint64_t s_id[BIN_SLOTS];
+  __shared__ uint8_t s_bin[BIN_SLOTS];
+  __shared__ uint32_t s_wcnt[BIN_WAVES][BIN_SLOTS];
+  __shared__ uint32_t s_off[BIN_SLOTS];
+  __shared__ uint8_t s_key[ENC_SMALL_MAX];
+  __shared__ uint32_t sh16[16];
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const uint32_t n = min(bin_n(a), ENC_SMALL_MAX);  // (hb_egress_bin sends no larger cap here)
+  bin_table_load(a, s_id, s_bin);
+  if (tid < BIN_SLOTS) s_off[tid] = 0;
+  __syncthreads();
+  for (uint32_t i = tid; i < n; i += BIN_THREADS) {
+    const uint32_t b = bin_of(s_id, s_bin, a.np, a.i_info[i], a.i_to[i]);
+    s_key[i] = (uint8_t)b;
+    atomicAdd(&s_off[b], 1u);
+  }
+  __syncthreads();
+  {
+    const uint32_t c = tid < BIN_SLOTS ? s_off[tid] : 0u;
+    uint32_t tot;
+    const uint32_t excl = block_excl_scan(c, sh16, &tot);  // (ends on a barrier: every count is read)
+    if (tid < BIN_SLOTS) s_off[tid] = excl;
+    if (tid <= a.np) a.bin_off[tid] = excl;
+    if (tid == 0) a.bin_off[a.np + 1] = tot;
+  }
+  for (uint32_t t0 = 0; t0 < n; t0 += BIN_TILE) {
+    uint32_t key[BIN_ROUNDS], dest[BIN_ROUNDS], idx[BIN_ROUNDS];
+    bool valid[BIN_ROUNDS];
+    BinRec rec[BIN_ROUNDS];
+#pragma unroll
+    for (uint32_t r = 0; r < BIN_ROUNDS; ++r) {
+      idx[r] = t0 + wave * (64 * BIN_ROUNDS) + r * 64 + lane;
+      valid[r] = idx[r] < n;
+      key[r] = valid[r] ? (uint32_t)s_key[idx[r]] : 0u;
+      if (valid[r]) bin_rec_load(a, idx[r], &rec[r]);
+    }
+    bin_rank_tile(key, valid, s_wcnt, s_off, dest);
+#pragma unroll
+    for (uint32_t r = 0; r < BIN_ROUNDS; ++r)
+      if (valid[r]) bin_rec_store(a, dest[r], idx[r], n, rec[r]);
+  }
+}
+// span[b] = off[bin_off[b]], b in [0, np + 1]
+__global__ void __launch_bounds__(BIN_SLOTS + 64) k_peer_spans(const uint64_t* off, const uint64_t* bin_off,
+                                                               uint64_t* span, uint32_t np) {
+  const uint32_t b = threadIdx.x;
+  if (b <= np + 1) span[b] = off[bin_off[b]];
+}
+
+// ============================================================================
 // host side
 // ============================================================================
 // What one step's prep (partition + route) hands to its apply.  Two sets, so
@@ -4075,6 +4444,11 @@ struct hb_handle {
   uint64_t* last0 = nullptr;      // [G] the last column before it
   uint32_t* eg_cnt = nullptr;     // [2 NB] records per chunk
   uint64_t* eg_base = nullptr;    // [2 NB + 1] their scan
+  // per-peer egress (hb_set_egress_peers / hb_egress_bin): nothing of it exists before the first table
+  BinTable* bin_table = nullptr;  // device copy of the node table
+  uint32_t bin_np = 0;            // its ids (the table is set while bin_table is)
+  uint8_t* bin_key = nullptr;     // [largest batch] key bytes of the tiled path (allocated on first use)
+  uint32_t* bin_hist = nullptr;   // [256] bin totals, then [256][its tiles] tile histograms
   uint32_t* enc_sum = nullptr;    // hb_encode: [blocks] bytes per pass-one workgroup (allocated on first use)
   uint64_t* enc_base = nullptr;   // [blocks + 1]
   uint64_t* rnd = nullptr;        // the r.rand stream (hb_set_rand), grown on demand
@@ -4536,7 +4910,7 @@ int hb_destroy(hb_handle* h) {
   if (h->dec_q) (void)hipFree(h->dec_q);
   if (h->dec_qn) (void)hipFree(h->dec_qn);
   for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->eg_cnt, (void*)h->eg_base, (void*)h->enc_sum,
-                  (void*)h->enc_base})
+                  (void*)h->enc_base, (void*)h->bin_table, (void*)h->bin_key, (void*)h->bin_hist})
     if (p) (void)hipFree(p);
   if (h->in_ready) (void)hipEventDestroy(h->in_ready);
   if (h->prep) (void)hipStreamDestroy(h->prep);
@@ -5585,6 +5959,114 @@ int hb_encode(hb_handle* h, const hb_out_batch* in, uint64_t cap, const uint64_t
   hipLaunchKernelGGL(k_enc_size, dim3(nblk), dim3(ENC_THREADS), 0, h->stream, ea);
   hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(1024), 0, h->stream, ea, nblk);
   hipLaunchKernelGGL(k_enc_write, dim3(nblk), dim3(ENC_THREADS), 0, h->stream, ea, nblk);
+  return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
+}
+
+// ---- per-peer egress -------------------------------------------------------------
+int hb_set_egress_peers(hb_handle* h, const uint64_t* ids, uint32_t n) {
+  if (!h || n > HB_EGRESS_MAX_PEERS || (n && !ids)) return HB_EINVAL;
+  BinTable t;
+  if (!bin_build(ids, n, &t)) return HB_EINVAL;
+  DeviceGuard guard(h->device);
+  if (n == 0) {
+    if (!h->bin_table) return HB_OK;
+    HB_CHECK(hipStreamSynchronize(h->stream));  // an hb_egress_bin may still read them
+    for (void* p : {(void*)h->bin_table, (void*)h->bin_key, (void*)h->bin_hist})
+      if (p) (void)hipFree(p);
+    h->bin_table = nullptr;
+    h->bin_key = nullptr;
+    h->bin_hist = nullptr;
+    h->bin_np = 0;
+    return HB_OK;
+  }
+  if (!h->bin_table && hipMalloc(&h->bin_table, sizeof(BinTable)) != hipSuccess) {
+    h->bin_table = nullptr;
+    return HB_ENOMEM;
+  }
+  // on the stream, after the hb_egress_bin calls made so far; `t` lives on this stack
+  HB_CHECK(hipMemcpyAsync(h->bin_table, &t, sizeof(BinTable), hipMemcpyHostToDevice, h->stream));
+  HB_CHECK(hipStreamSynchronize(h->stream));
+  h->bin_np = n;
+  return HB_OK;
+}
+
+int hb_egress_bin(hb_handle* h, const hb_out_batch* in, uint64_t cap, const uint64_t* n_dev, const hb_out_batch* out,
+                  uint32_t* src, uint64_t* bin_off) {
+  if (!h || !in || !out || !bin_off) return HB_EINVAL;
+  if (!in->group || !in->info || !in->to || !in->term || !in->log_term || !in->index || !in->commit || !in->hint)
+    return HB_EINVAL;
+  if (!out->group || !out->info || !out->to || !out->term || !out->log_term || !out->index || !out->commit ||
+      !out->hint)
+    return HB_EINVAL;
+  if (out->group == in->group || out->info == in->info || out->to == in->to || out->term == in->term ||
+      out->log_term == in->log_term || out->index == in->index || out->commit == in->commit ||
+      out->hint == in->hint)
+    return HB_EINVAL;
+  if (!h->bin_table) return HB_EINVAL;
+  // (record numbers, src among them, are 32-bit)
+  if (cap > h->max_batch * (h->nmax + 4ull) || cap >= (1ull << 32)) return HB_EINVAL;
+  DeviceGuard guard(h->device);
+  BinArgs a;
+  a.i_group = in->group;
+  a.i_info = in->info;
+  a.i_to = in->to;
+  a.i_term = in->term;
+  a.i_log_term = in->log_term;
+  a.i_index = in->index;
+  a.i_commit = in->commit;
+  a.i_hint = in->hint;
+  a.o_group = out->group;
+  a.o_info = out->info;
+  a.o_to = out->to;
+  a.o_term = out->term;
+  a.o_log_term = out->log_term;
+  a.o_index = out->index;
+  a.o_commit = out->commit;
+  a.o_hint = out->hint;
+  a.src = src;
+  a.bin_off = dev_view(bin_off);
+  a.table = h->bin_table;
+  a.np = h->bin_np;
+  a.cap = (uint32_t)cap;
+  a.n_dev = dev_view(n_dev);
+  a.key = nullptr;
+  a.hist = nullptr;
+  a.tot = nullptr;
+  a.ntiles = 0;
+  if (cap == 0 || (cap <= ENC_SMALL_MAX && !h->no_small)) {
+    hipLaunchKernelGGL(k_bin_small, dim3(1), dim3(BIN_THREADS), 0, h->stream, a);
+    return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
+  }
+  if (!h->bin_key) {  // once, for the largest batch the handle takes
+    const uint64_t cm = std::min<uint64_t>(h->max_batch * (h->nmax + 4ull), (1ull << 32) - 1);
+    const uint64_t nt = (cm + BIN_TILE - 1) / BIN_TILE;
+    if (hipMalloc(&h->bin_key, cm) != hipSuccess) {
+      h->bin_key = nullptr;
+      return HB_ENOMEM;
+    }
+    if (hipMalloc(&h->bin_hist, (nt + 1) * BIN_SLOTS * 4) != hipSuccess) {  // the bins' totals, then their rows
+      (void)hipFree(h->bin_key);
+      h->bin_key = nullptr;
+      h->bin_hist = nullptr;
+      return HB_ENOMEM;
+    }
+  }
+  a.key = h->bin_key;
+  a.tot = h->bin_hist;
+  a.hist = h->bin_hist + BIN_SLOTS;
+  a.ntiles = (uint32_t)((cap + BIN_TILE - 1) / BIN_TILE);
+  hipLaunchKernelGGL(k_bin_hist, dim3(a.ntiles), dim3(BIN_THREADS), 0, h->stream, a);
+  hipLaunchKernelGGL(k_bin_scan, dim3(a.np + 1), dim3(1024), 0, h->stream, a);
+  hipLaunchKernelGGL(k_bin_scatter, dim3(a.ntiles), dim3(BIN_THREADS), 0, h->stream, a);
+  return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
+}
+
+int hb_peer_spans(hb_handle* h, const uint64_t* off, const uint64_t* bin_off, uint64_t* span) {
+  if (!h || !off || !bin_off || !span) return HB_EINVAL;
+  if (!h->bin_table) return HB_EINVAL;
+  DeviceGuard guard(h->device);
+  hipLaunchKernelGGL(k_peer_spans, dim3(1), dim3(BIN_SLOTS + 64), 0, h->stream, off, dev_view(bin_off), dev_view(span),
+                     h->bin_np);
   return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
 }
 

@@ -125,6 +125,10 @@ def lib():
         "hb_egress": (C.c_int, [H, C.c_uint64, P(abi.hb_out_batch), C.c_uint64, C.c_void_p]),
         "hb_encode": (C.c_int, [H, P(abi.hb_out_batch), C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+        "hb_set_egress_peers": (C.c_int, [H, C.c_void_p, C.c_uint32]),
+        "hb_egress_bin": (C.c_int, [H, P(abi.hb_out_batch), C.c_uint64, C.c_void_p, P(abi.hb_out_batch), C.c_void_p,
+                                    C.c_void_p]),
+        "hb_peer_spans": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
         "hb_events_device": (C.c_int, [H, P(C.c_void_p), P(C.c_void_p), P(C.c_void_p), P(C.c_uint32)]),
         "hb_copy_events": (C.c_int, [H, C.c_void_p, C.c_uint64, P(C.c_uint64)]),
         "hb_events_to_host": (C.c_int, [H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
@@ -380,6 +384,28 @@ class Engine:
         self._keep_enc = (batch, data, off, status, total, n_dev)
         _check("hb_encode", lib().hb_encode(self.h, C.byref(b), cap, _ptr(n_dev), self_id, _ptr(data),
                                             0 if data is None else len(data), _ptr(off), _ptr(status), _ptr(total)))
+
+    def set_egress_peers(self, ids):
+        """hb_set_egress_peers: the node table of egress_bin(); bin b is ids[b], bin len(ids)
+        is "other".  At most HB_EGRESS_MAX_PEERS distinct non-zero ids; an empty list frees it."""
+        a = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        _check("hb_set_egress_peers", lib().hb_set_egress_peers(self.h, a.ctypes.data if len(a) else None, len(a)))
+
+    def egress_bin(self, batch, cap, out, bin_off, src=None, n_dev=None):
+        """hb_egress_bin: the records of `batch` (an egress() out dict) split stably by destination
+        node into the device tensors of `out` (the same eight arrays, none shared with `batch`);
+        bin_off = device (or pinned) u64 [len(ids) + 2], src = optional device u32 [cap] (the input
+        index of every output record), n_dev = a device (or pinned) u64 (None: cap records)."""
+        bi, bo = self._out_batch(batch), self._out_batch(out)
+        self._keep_bin = (batch, out, bin_off, src, n_dev)
+        _check("hb_egress_bin", lib().hb_egress_bin(self.h, C.byref(bi), cap, _ptr(n_dev), C.byref(bo), _ptr(src),
+                                                    _ptr(bin_off)))
+
+    def peer_spans(self, off, bin_off, span):
+        """hb_peer_spans: span[b] = off[bin_off[b]] (device or pinned u64 [len(ids) + 2]); with `off`
+        from an encode() of the binned batch, peer b's bytes are data[span[b]:span[b + 1]]."""
+        self._keep_span = (off, bin_off, span)
+        _check("hb_peer_spans", lib().hb_peer_spans(self.h, _ptr(off), _ptr(bin_off), _ptr(span)))
 
     def step_batch(self, batch, **kw):
         return self.step(batch["group"], batch["info"], batch["term"], batch["index"],

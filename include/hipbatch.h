@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define HB_ABI_VERSION 7
+#define HB_ABI_VERSION 8
 
 /* ---- error codes -------------------------------------------------------- */
 #define HB_OK          0
@@ -589,6 +589,43 @@ int  hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t
 int  hb_encode(hb_handle* h, const hb_out_batch* in, uint64_t cap, const uint64_t* n_dev, uint64_t self_id,
                uint8_t* bytes, uint64_t bytes_cap, uint64_t* off /* [cap + 1] */, uint8_t* status /* [cap] */,
                uint64_t* total);
+
+/* ---- per-peer egress -----------------------------------------------------
+ * A transport has one stream per remote node: it needs one contiguous byte
+ * span per destination, each group's messages still in r.msgs order inside
+ * it.  hb_egress_bin is a stable split of a record batch by destination node,
+ * between hb_egress and hb_encode; the per-peer byte spans then fall out of
+ * hb_encode's off[].  The chain hb_egress -> hb_egress_bin -> hb_encode (on
+ * `out`) -> hb_peer_spans runs on the handle's stream and is fed by hb_egress's
+ * device count: no host round trip.  Without a node table nothing is
+ * allocated or launched. */
+#define HB_EGRESS_MAX_PEERS 255
+/* The node table of hb_egress_bin: n distinct non-zero node ids (host memory), n <= 255.
+ * Bin b is ids[b] (the caller's order); bin n is "other".  n = 0 frees the table.
+ * HB_EINVAL before any device work: NULL handle, n > 255, ids NULL with n > 0,
+ * a zero or repeated id.  Stream-ordered against earlier hb_egress_bin calls
+ * (it waits for the handle's stream: a configuration call). */
+int  hb_set_egress_peers(hb_handle* h, const uint64_t* ids, uint32_t n);
+/* Stable split of the first n records of `in` by destination:
+ * n = *n_dev clamped to cap, or cap when n_dev is NULL (as hb_encode).
+ * out = the same records, bin-major, and inside a bin in the order they had in `in`.
+ * bin_off[b], b in [0, n_peers + 1]: first output record of bin b;
+ * bin_off[n_peers + 1] = n.  So (n_peers + 2) u64 words of device or pinned memory.
+ * src[j] (optional, may be NULL) = the index in `in` of output record j.
+ * Bin of a record: to_ref == HB_REF_OTHER -> "other"; else the b with ids[b] == to
+ * (all 64 bits); no such b -> "other".
+ * Records of `out` (and src) at and past n are not written; `in` is not written.
+ * n = 0 and cap = 0 are legal: bin_off is then all zeros.
+ * HB_EINVAL before any device work: NULL handle / batch / array / bin_off, no table set,
+ * cap > max_batch x (max_replicas + 4) or cap >= 2^32, any array of `out` equal to
+ * the same array of `in`.  Asynchronous on the handle's stream. */
+int  hb_egress_bin(hb_handle* h, const hb_out_batch* in, uint64_t cap, const uint64_t* n_dev,
+                   const hb_out_batch* out, uint32_t* src, uint64_t* bin_off);
+/* span[b] = off[bin_off[b]] for b in [0, n_peers + 1]: with `off` from an hb_encode of the
+ * binned batch, peer b's bytes are bytes[span[b], span[b+1]).  One small launch, so that a
+ * transport reads n_peers + 2 words instead of two per-record arrays.  span: device or
+ * pinned memory.  HB_EINVAL: a NULL argument, no table set. */
+int  hb_peer_spans(hb_handle* h, const uint64_t* off, const uint64_t* bin_off, uint64_t* span);
 
 /* ---- the hot path ----------------------------------------------------------
  * Step one batch (all messages of the batch, per group in arrival order).
