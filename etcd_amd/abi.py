@@ -24,6 +24,9 @@ HB_NO_INDEX = (1 << 64) - 1
 HB_SIZE_RING_MIN = 16
 HB_TERM_RING_MIN = 8
 HB_INFO_VOTED = 0x200
+HB_OUT_HOST = 0x400      # hb_out_batch info: a MsgVote record the host builds (LogTerm unknown)
+HB_EGRESS_ON = 1
+HB_EGRESS_VOTES = 2       # hb_set_egress bit: MsgVote records
 HB_ENT_MAX_DATA = 0x3FFFFFFF
 
 # StateType raft/raft.go:35-39

@@ -3595,14 +3595,15 @@ __device__ __forceinline__ uint64_t enc_n(const EncodeArgs& a) {
   const uint64_t n = a.n_dev ? *a.n_dev : a.cap;
   return n < a.cap ? n : a.cap;
 }
-// record i and its encoded length (0: past the end, or HB_REF_OTHER: the host knows the id)
+// record i and its encoded length (0: past the end, HB_REF_OTHER: the host knows the id, or
+// HB_OUT_HOST: a MsgVote whose LogTerm the replay could not tell)
 __device__ __forceinline__ uint32_t enc_load(const EncodeArgs& a, uint64_t i, uint64_t n, EncRec* r) {
   r->host = false;
   if (i >= n) return 0;
   const uint32_t info = a.info[i];
   r->type = info & 0xF;
   r->reject = (info >> 8) & 1u;
-  r->host = ((info >> 4) & 0xF) == HB_REF_OTHER;
+  r->host = ((info >> 4) & 0xF) == HB_REF_OTHER || (info & HB_OUT_HOST) != 0;
   if (r->host) return 0;
   r->to = a.to[i];
   r->term = a.term[i];
@@ -3709,7 +3710,8 @@ __global__ void __launch_bounds__(ENC_SMALL_THREADS) k_enc_small(EncodeArgs a) {
 // per partition (its P chunk, then its M chunk), one lane per group.  The
 // words of a chunk interleave the partition's groups in emission order, and a
 // record's place in the output is fixed by its word's place in the chunk: a
-// per-word "makes a record" flag (a response or a heartbeat; the engine emits
+// per-word record count (1 for a response or a heartbeat, in vote mode 1 for
+// a vote and the mask's population for a vote broadcast; the engine emits
 // nothing for a group after its HB_EV_FAULT), a block scan per tile, a
 // running base per chunk, chunk bases from a scan over the chunks.  A chunk
 // goes through LDS in tiles of EG_TILE words; every lane then walks the tile's
@@ -3721,6 +3723,7 @@ struct EgressArgs {
   const uint32_t* ev_counts;
   uint32_t nc, G;
   const uint64_t *term0, *last0, *peer;
+  const uint64_t* lterm0;  // [G] vote mode: lastTerm before the step, or HB_LT_UNKNOWN (else null)
   uint32_t* ccnt;    // [nc] records per chunk
   uint64_t* cbase;   // [nc + 1] their exclusive scan, then the total
   uint64_t cap;
@@ -3728,21 +3731,30 @@ struct EgressArgs {
   uint32_t *o_group, *o_info;
   uint64_t *o_to, *o_term, *o_log_term, *o_index, *o_commit, *o_hint;
 };
+constexpr uint64_t HB_LT_UNKNOWN = ~0ull;  // lterm0 / the replay's lastTerm: not known to the device
 constexpr uint32_t EG_TILE = 2048;  // words of a chunk in LDS at a time (8 per lane)
 constexpr uint32_t EG_PER = EG_TILE / PART;
 constexpr uint32_t EG_SMALL = 1024;  // chunks the one-workgroup count + scan takes
 static_assert(EG_PER == 8, "a lane's group bytes of a tile are one 8-byte LDS store");
 
+// The records a word makes.  VOTES (hb_set_egress bit HB_EGRESS_VOTES): campaign's MsgVotes too,
+// one for an HB_EV_VOTE word and one per slot of an EVC_VBCAST word's mask.
+template <bool VOTES>
 __device__ __forceinline__ uint32_t eg_record(uint64_t w) {
   const uint32_t t = (uint32_t)w & 0xF;
+  if (VOTES) {
+    if (t == EVC_VBCAST) return (uint32_t)__popc((uint32_t)(w >> 4) & 0x7Fu);
+    if (t == HB_EV_VOTE) return 1u;
+  }
   return (t == HB_EV_RESP || t == HB_EV_HEARTBEAT) ? 1u : 0u;
 }
+template <bool VOTES>
 __global__ void __launch_bounds__(256) k_eg_count(EgressArgs a) {
   __shared__ uint32_t sh16[16];
   const uint32_t c = blockIdx.x, n = a.ev_counts[c];
   const uint64_t* src = a.ev + a.ev_off[c];
   uint32_t k = 0;
-  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) k += eg_record(src[i]);
+  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) k += eg_record<VOTES>(src[i]);
   uint32_t tot;
   (void)block_excl_scan(k, sh16, &tot);
   if (threadIdx.x == 0) a.ccnt[c] = tot;
@@ -3764,6 +3776,7 @@ __global__ void __launch_bounds__(1024) k_eg_scan(EgressArgs a) {
   }
 }
 // Count and scan in one workgroup when the chunks are few: a wave per chunk counts.
+template <bool VOTES>
 __global__ void __launch_bounds__(1024) k_eg_small(EgressArgs a) {
   __shared__ uint32_t sh16[16];
   __shared__ uint32_t s_cnt[EG_SMALL];
@@ -3772,7 +3785,7 @@ __global__ void __launch_bounds__(1024) k_eg_small(EgressArgs a) {
     const uint32_t n = a.ev_counts[c];
     const uint64_t* src = a.ev + a.ev_off[c];
     uint32_t k = 0;
-    for (uint32_t i = lane; i < n; i += 64) k += eg_record(src[i]);
+    for (uint32_t i = lane; i < n; i += 64) k += eg_record<VOTES>(src[i]);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) k += __shfl_xor(k, d);
     if (lane == 0) s_cnt[c] = k;
@@ -3788,6 +3801,7 @@ __global__ void __launch_bounds__(1024) k_eg_small(EgressArgs a) {
   }
 }
 
+template <bool VOTES>
 __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
   __shared__ uint64_t s_w[EG_TILE];
   __shared__ uint32_t s_pos[EG_TILE];
@@ -3796,6 +3810,8 @@ __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
   const uint32_t tid = threadIdx.x, part = blockIdx.x, g = part * PART + tid;
   const bool live = g < a.G;
   uint64_t term = live ? a.term0[g] : 0ull, last = live ? a.last0[g] : 0ull;
+  uint64_t lt = 0;  // VOTES: raftLog.lastTerm() at this point of the replay, or HB_LT_UNKNOWN
+  if (VOTES) lt = live ? a.lterm0[g] : 0ull;
   bool pend = false, dead = false;
   const uint32_t pat = tid * 0x01010101u;
   for (uint32_t c = 2 * part; c < 2 * part + 2; ++c) {
@@ -3811,7 +3827,7 @@ __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
       for (uint32_t j = 0; j < EG_PER; ++j) {
         const uint32_t li = tid * EG_PER + j;
         w[j] = li < m ? src[t0 + li] : (uint64_t)EVC_CONT;
-        k += eg_record(w[j]);
+        k += eg_record<VOTES>(w[j]);
       }
       uint32_t tot;
       uint32_t pos = block_excl_scan(k, sh16, &tot);
@@ -3821,7 +3837,7 @@ __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
         const uint32_t li = tid * EG_PER + j;
         s_w[li] = w[j];
         s_pos[li] = pos;
-        pos += eg_record(w[j]);
+        pos += eg_record<VOTES>(w[j]);
         const uint32_t kb = (uint32_t)(w[j] >> 16) & 0xFF;
         if (j < 4) klo |= kb << (8 * j);
         else khi |= kb << (8 * (j - 4));
@@ -3850,10 +3866,33 @@ __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
               xv |= (cw >> 4) << 40;
             }
             if (type == HB_EV_TERM) term = xv;
-            else if (type == HB_EV_LAST) last = xv;
-            else if (type == HB_EV_FOLLOW) pend |= aux == HB_FOLLOW_APPEND || aux == HB_FOLLOW_RESTORE;
-            else if (type == HB_EV_FAULT) dead = true;
-            else if (type == HB_EV_RESP || type == HB_EV_HEARTBEAT) {
+            else if (type == HB_EV_LAST) {
+              last = xv;
+              if (VOTES) lt = term;  // appendEntry: the group's own entries carry its Term
+            } else if (type == HB_EV_FOLLOW) {
+              const bool app = aux == HB_FOLLOW_APPEND || aux == HB_FOLLOW_RESTORE;
+              pend |= app;
+              if (VOTES && app) lt = HB_LT_UNKNOWN;  // the events hold no terms of a leader's entries
+            } else if (type == HB_EV_FAULT) dead = true;
+            else if (VOTES && (type == HB_EV_VOTE || type == EVC_VBCAST)) {
+              // campaign's MsgVote (raft/raft.go:429-443): one record per slot, in slot order; a
+              // LogTerm the replay cannot tell leaves the record to the host (HB_OUT_HOST)
+              const bool known = lt != HB_LT_UNKNOWN;
+              uint32_t mask = type == EVC_VBCAST ? to : 1u << (to <= HB_REF_SLOT_MAX ? to : 7u);
+              for (uint64_t o = run + s_pos[li]; mask && o < a.cap; mask &= mask - 1, ++o) {
+                const uint32_t s = (uint32_t)__ffs(mask) - 1;
+                const bool slot = s <= HB_REF_SLOT_MAX;  // (no lane sends a MsgVote outside prs)
+                a.o_group[o] = g;
+                a.o_info[o] = HB_INFO(HB_MSG_VOTE, slot ? s : (uint32_t)HB_REF_OTHER, false) |
+                              (known ? 0u : (uint32_t)HB_OUT_HOST);
+                a.o_to[o] = slot ? a.peer[(size_t)g * HB_PEER_ROW + s] : 0ull;
+                a.o_term[o] = term;
+                a.o_log_term[o] = known ? lt : 0ull;
+                a.o_index[o] = xv;
+                a.o_commit[o] = 0;
+                a.o_hint[o] = 0;
+              }
+            } else if (type == HB_EV_RESP || type == HB_EV_HEARTBEAT) {
               uint32_t mtype = HB_MSG_HEARTBEAT;
               uint64_t index = 0, commit = 0, hint = 0;
               bool reject = false;
@@ -3896,16 +3935,58 @@ __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
   }
 }
 
-// The pre-step snapshot of the term and last columns (hb_set_egress).
-__global__ void __launch_bounds__(256) k_eg_snap(const uint64_t* term, const uint64_t* last, uint64_t* term0,
-                                                 uint64_t* last0, uint32_t G) {
+// The pre-step snapshot of the term and last columns (hb_set_egress).  VOTES: also
+// lterm0 = raftLog.lastTerm() as Lane::fterm(last) gives it: Term inside the
+// current-term run [tfirst, last], else the newest older run of the ring at or
+// below last (only those groups read the ring), HB_LT_UNKNOWN when the ring
+// does not reach (runs never loaded).
+struct SnapArgs {
+  const uint64_t *term, *last;
+  uint64_t *term0, *last0;
+  uint32_t G;
+  const uint64_t *tfirst, *trx, *trc;  // VOTES only
+  uint64_t* lterm0;
+};
+__device__ __forceinline__ uint64_t eg_last_term(const SnapArgs& a, uint32_t g, uint64_t term, uint64_t last) {
+  const uint64_t tf = a.tfirst[g];
+  if (tf != HB_NO_INDEX && last >= tf) return term;
+  const uint64_t x = a.trx[g], c = a.trc[g];
+  Runs r;
+  r.R = lx_base(x);
+  r.mask = lx_cap(x) - 1;
+  r.n = (uint32_t)c;
+  r.h = (uint32_t)(c >> 32);
+  bool ok = true;
+  const uint64_t t = r.find(last, &ok);
+  return ok ? t : HB_LT_UNKNOWN;
+}
+template <bool VOTES>
+__global__ void __launch_bounds__(256) k_eg_snap(SnapArgs a) {
   const uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) * 2;
+  const uint32_t G = a.G;
+  if (!VOTES) {
+    if (i + 1 < G) {
+      *reinterpret_cast<uint4*>(a.term0 + i) = *reinterpret_cast<const uint4*>(a.term + i);
+      *reinterpret_cast<uint4*>(a.last0 + i) = *reinterpret_cast<const uint4*>(a.last + i);
+    } else if (i < G) {
+      a.term0[i] = a.term[i];
+      a.last0[i] = a.last[i];
+    }
+    return;
+  }
   if (i + 1 < G) {
-    *reinterpret_cast<uint4*>(term0 + i) = *reinterpret_cast<const uint4*>(term + i);
-    *reinterpret_cast<uint4*>(last0 + i) = *reinterpret_cast<const uint4*>(last + i);
+    const uint4 t = *reinterpret_cast<const uint4*>(a.term + i), l = *reinterpret_cast<const uint4*>(a.last + i);
+    *reinterpret_cast<uint4*>(a.term0 + i) = t;
+    *reinterpret_cast<uint4*>(a.last0 + i) = l;
+    const uint64_t lt0 = eg_last_term(a, i, (uint64_t)t.x | ((uint64_t)t.y << 32), (uint64_t)l.x | ((uint64_t)l.y << 32));
+    const uint64_t lt1 = eg_last_term(a, i + 1, (uint64_t)t.z | ((uint64_t)t.w << 32), (uint64_t)l.z | ((uint64_t)l.w << 32));
+    *reinterpret_cast<uint4*>(a.lterm0 + i) =
+        make_uint4((uint32_t)lt0, (uint32_t)(lt0 >> 32), (uint32_t)lt1, (uint32_t)(lt1 >> 32));
   } else if (i < G) {
-    term0[i] = term[i];
-    last0[i] = last[i];
+    const uint64_t t = a.term[i], l = a.last[i];
+    a.term0[i] = t;
+    a.last0[i] = l;
+    a.lterm0[i] = eg_last_term(a, i, t, l);
   }
 }
 
@@ -4440,6 +4521,8 @@ struct hb_handle {
   // wire egress (hb_set_egress / hb_egress / hb_encode): nothing of it exists while egress is off
   bool egress = false;
   bool eg_stepped = false;        // a step or tick has run since hb_set_egress(on)
+  bool eg_votes = false;          // HB_EGRESS_VOTES: MsgVote records, the lterm0 column
+  uint64_t* lterm0 = nullptr;     // [G] raftLog.lastTerm() before the last step / tick, or HB_LT_UNKNOWN
   uint64_t* term0 = nullptr;      // [G] the term column before the last step / tick
   uint64_t* last0 = nullptr;      // [G] the last column before it
   uint32_t* eg_cnt = nullptr;     // [2 NB] records per chunk
@@ -4602,10 +4685,21 @@ uint32_t apply_grid_for(uint32_t NBK, uint32_t sl, uint32_t NB) {
 }
 uint32_t apply_grid(const hb_handle* h) { return h->agrid; }
 
-// hb_set_egress: the group's Term and lastIndex before the step (one launch, 32 B per group moved)
+// hb_set_egress: the group's Term and lastIndex before the step (one launch, 32 B per group moved;
+// vote mode: lastTerm too, 16 B per group more and a ring lookup for a last index below the current-term run)
 void egress_snapshot(hb_handle* h, hipStream_t st) {
-  hipLaunchKernelGGL(k_eg_snap, dim3((h->G + 511) / 512), dim3(256), 0, st, (const uint64_t*)h->st.term,
-                     (const uint64_t*)h->st.last, h->term0, h->last0, h->G);
+  SnapArgs a;
+  a.term = h->st.term;
+  a.last = h->st.last;
+  a.term0 = h->term0;
+  a.last0 = h->last0;
+  a.G = h->G;
+  a.tfirst = h->st.tfirst;
+  a.trx = h->st.trx;
+  a.trc = h->st.trc;
+  a.lterm0 = h->lterm0;
+  if (h->eg_votes) hipLaunchKernelGGL(k_eg_snap<true>, dim3((h->G + 511) / 512), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_eg_snap<false>, dim3((h->G + 511) / 512), dim3(256), 0, st, a);
   h->eg_stepped = true;
 }
 // A device-readable word the caller names: pinned host memory (hb_alloc_pinned) or device memory.
@@ -4909,7 +5003,7 @@ int hb_destroy(hb_handle* h) {
   if (h->peer) (void)hipFree(h->peer);
   if (h->dec_q) (void)hipFree(h->dec_q);
   if (h->dec_qn) (void)hipFree(h->dec_qn);
-  for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->eg_cnt, (void*)h->eg_base, (void*)h->enc_sum,
+  for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->lterm0, (void*)h->eg_cnt, (void*)h->eg_base, (void*)h->enc_sum,
                   (void*)h->enc_base, (void*)h->bin_table, (void*)h->bin_key, (void*)h->bin_hist})
     if (p) (void)hipFree(p);
   if (h->in_ready) (void)hipEventDestroy(h->in_ready);
@@ -5838,29 +5932,53 @@ int hb_events_to_host(hb_handle* h, uint64_t* words, uint64_t cap, uint32_t* cou
 int hb_set_egress(hb_handle* h, int on) {
   if (!h) return HB_EINVAL;
   DeviceGuard guard(h->device);
+  const bool votes = on && (on & HB_EGRESS_VOTES);
+  if (h->egress && (!on || votes != h->eg_votes))
+    HB_CHECK(hipStreamSynchronize(h->stream));  // an hb_egress may still read the columns
   if (!on) {
     if (!h->egress) return HB_OK;
-    HB_CHECK(hipStreamSynchronize(h->stream));  // an hb_egress may still read them
-    for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->eg_cnt, (void*)h->eg_base})
+    for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->lterm0, (void*)h->eg_cnt, (void*)h->eg_base})
       if (p) (void)hipFree(p);
-    h->term0 = h->last0 = h->eg_base = nullptr;
+    h->term0 = h->last0 = h->lterm0 = h->eg_base = nullptr;
     h->eg_cnt = nullptr;
-    h->egress = false;
+    h->egress = h->eg_votes = false;
     return HB_OK;
   }
-  if (h->egress) return HB_OK;
   const size_t G = h->G, nc = 2 * (size_t)h->NB;
+  if (h->egress) {
+    if (votes == h->eg_votes) return HB_OK;
+    // the mode changes: the step before this call has no matching snapshot
+    if (votes) {
+      if (hipMalloc(&h->lterm0, G * 8) != hipSuccess) {
+        h->lterm0 = nullptr;
+        return HB_ENOMEM;
+      }
+    } else {
+      (void)hipFree(h->lterm0);
+      h->lterm0 = nullptr;
+    }
+    h->eg_votes = votes;
+    h->eg_stepped = false;
+    return HB_OK;
+  }
   if (hipMalloc(&h->term0, G * 8) != hipSuccess || hipMalloc(&h->last0, G * 8) != hipSuccess ||
-      hipMalloc(&h->eg_cnt, nc * 4) != hipSuccess || hipMalloc(&h->eg_base, (nc + 1) * 8) != hipSuccess) {
-    for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->eg_cnt, (void*)h->eg_base})
+      hipMalloc(&h->eg_cnt, nc * 4) != hipSuccess || hipMalloc(&h->eg_base, (nc + 1) * 8) != hipSuccess ||
+      (votes && hipMalloc(&h->lterm0, G * 8) != hipSuccess)) {
+    for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->lterm0, (void*)h->eg_cnt, (void*)h->eg_base})
       if (p) (void)hipFree(p);
-    h->term0 = h->last0 = h->eg_base = nullptr;
+    h->term0 = h->last0 = h->lterm0 = h->eg_base = nullptr;
     h->eg_cnt = nullptr;
     return HB_ENOMEM;
   }
   h->egress = true;
+  h->eg_votes = votes;
   h->eg_stepped = false;  // the step before this call has no snapshot: its events are not replayed
   return HB_OK;
+}
+
+int hb_egress_mode(hb_handle* h) {
+  if (!h) return HB_EINVAL;
+  return h->egress ? (HB_EGRESS_ON | (h->eg_votes ? HB_EGRESS_VOTES : 0)) : 0;
 }
 
 int hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t cap, uint64_t* count) {
@@ -5886,6 +6004,7 @@ int hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t 
   ea.term0 = h->term0;
   ea.last0 = h->last0;
   ea.peer = h->peer;
+  ea.lterm0 = h->lterm0;
   ea.ccnt = h->eg_cnt;
   ea.cbase = h->eg_base;
   ea.cap = cap;
@@ -5898,13 +6017,17 @@ int hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t 
   ea.o_index = out->index;
   ea.o_commit = out->commit;
   ea.o_hint = out->hint;
-  if (ea.nc <= EG_SMALL && !h->no_small) {
-    hipLaunchKernelGGL(k_eg_small, dim3(1), dim3(1024), 0, h->stream, ea);
+  const bool small = ea.nc <= EG_SMALL && !h->no_small;
+  if (h->eg_votes) {
+    if (small) hipLaunchKernelGGL(k_eg_small<true>, dim3(1), dim3(1024), 0, h->stream, ea);
+    else hipLaunchKernelGGL(k_eg_count<true>, dim3(ea.nc), dim3(256), 0, h->stream, ea);
   } else {
-    hipLaunchKernelGGL(k_eg_count, dim3(ea.nc), dim3(256), 0, h->stream, ea);
-    hipLaunchKernelGGL(k_eg_scan, dim3(1), dim3(1024), 0, h->stream, ea);
+    if (small) hipLaunchKernelGGL(k_eg_small<false>, dim3(1), dim3(1024), 0, h->stream, ea);
+    else hipLaunchKernelGGL(k_eg_count<false>, dim3(ea.nc), dim3(256), 0, h->stream, ea);
   }
-  hipLaunchKernelGGL(k_egress, dim3(h->NB), dim3(PART), 0, h->stream, ea);
+  if (!small) hipLaunchKernelGGL(k_eg_scan, dim3(1), dim3(1024), 0, h->stream, ea);
+  if (h->eg_votes) hipLaunchKernelGGL(k_egress<true>, dim3(h->NB), dim3(PART), 0, h->stream, ea);
+  else hipLaunchKernelGGL(k_egress<false>, dim3(h->NB), dim3(PART), 0, h->stream, ea);
   return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
 }
 

@@ -122,6 +122,7 @@ def lib():
         "hb_decode": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, P(abi.hb_batch),
                                 C.c_void_p]),
         "hb_set_egress": (C.c_int, [H, C.c_int]),
+        "hb_egress_mode": (C.c_int, [H]),
         "hb_egress": (C.c_int, [H, C.c_uint64, P(abi.hb_out_batch), C.c_uint64, C.c_void_p]),
         "hb_encode": (C.c_int, [H, P(abi.hb_out_batch), C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -356,10 +357,19 @@ class Engine:
                                             C.byref(b), _ptr(status)))
 
     # ---- wire egress ---------------------------------------------------------------
-    def set_egress(self, on=True):
+    def set_egress(self, on=True, votes=False):
         """hb_set_egress: every later step / tick keeps the groups' Term and lastIndex
-        from before it, which egress() needs; off frees them."""
-        _check("hb_set_egress", lib().hb_set_egress(self.h, 1 if on else 0))
+        from before it, which egress() needs; off frees them.  votes: vote mode
+        (HB_EGRESS_VOTES), the lastTerm column too and campaign's MsgVote records."""
+        mode = (abi.HB_EGRESS_ON | (abi.HB_EGRESS_VOTES if votes else 0)) if on else 0
+        _check("hb_set_egress", lib().hb_set_egress(self.h, mode))
+
+    def egress_mode(self):
+        """hb_egress_mode: 0, HB_EGRESS_ON, or HB_EGRESS_ON | HB_EGRESS_VOTES."""
+        m = lib().hb_egress_mode(self.h)
+        if m < 0:
+            raise HipBatchError("hb_egress_mode", m)
+        return m
 
     @staticmethod
     def _out_batch(out):

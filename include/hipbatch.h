@@ -538,8 +538,9 @@ int  hb_decode(hb_handle* h, const uint8_t* bytes, const uint64_t* off, const ui
 
 /* ---- wire egress ---------------------------------------------------------
  * The send path's counterpart of hb_decode: the payload-free messages a step
- * or tick produces (MsgAppResp, MsgHeartbeatResp, MsgVoteResp, MsgHeartbeat:
- * no entries, the empty snapshot) leave the device as the bytes
+ * or tick produces (MsgAppResp, MsgHeartbeatResp, MsgVoteResp, MsgHeartbeat
+ * and, in vote mode, campaign's MsgVote: no entries, the empty snapshot) leave
+ * the device as the bytes
  * Message.MarshalTo writes (raft/raftpb/raft.pb.go:1271-1330), ready for the
  * transport, without the host replaying an event.  Two calls, both
  * asynchronous on the handle's stream:
@@ -548,7 +549,7 @@ int  hb_decode(hb_handle* h, const uint8_t* bytes, const uint64_t* off, const ui
  * A batch is a structure of arrays in device memory, capacity `cap` records: */
 typedef struct hb_out_batch {
   uint32_t* group;    /* group slot                                                   */
-  uint32_t* info;     /* HB_INFO(type, to_ref, reject); to_ref = slot or HB_REF_OTHER */
+  uint32_t* info;     /* HB_INFO(type, to_ref, reject) [| HB_OUT_HOST]; to_ref = slot or HB_REF_OTHER */
   uint64_t* to;       /* m.To as a node id (0 when to_ref == HB_REF_OTHER)            */
   uint64_t* term;     /* m.Term */
   uint64_t* log_term; /* m.LogTerm */
@@ -556,13 +557,32 @@ typedef struct hb_out_batch {
   uint64_t* commit;   /* m.Commit */
   uint64_t* hint;     /* m.RejectHint */
 } hb_out_batch;
-/* Egress on: every later hb_step / hb_tick first copies the groups' Term and
- * lastIndex columns (16 B per group, allocated here) so that hb_egress can
- * give each message the Term and each rejection the RejectHint of the point
- * of its send: the events are a delta, the state after the step holds only
- * the final values.  Off (the default): nothing is allocated, copied or
- * launched, and hb_egress returns HB_EINVAL. */
+/* Egress on (any non-zero `on`): every later hb_step / hb_tick first copies the
+ * groups' Term and lastIndex columns (16 B per group, allocated here) so that
+ * hb_egress can give each message the Term and each rejection the RejectHint
+ * of the point of its send: the events are a delta, the state after the step
+ * holds only the final values.  Off (the default): nothing is allocated,
+ * copied or launched, and hb_egress returns HB_EINVAL.
+ * Bit HB_EGRESS_VOTES of `on` adds vote mode: a third column, the log's
+ * lastTerm before the step (8 B per group more; a group whose last index lies
+ * below its current-term run reads its term-run ring), and hb_egress also
+ * makes campaign's MsgVote records.  Without the bit the snapshot and
+ * hb_egress's output are what they were before the bit existed.  A call that
+ * changes the mode while egress is on waits for the stream, allocates or frees
+ * the column, and hb_egress gives count 0 until the next step or tick (the
+ * step before the call has no matching snapshot). */
+#define HB_EGRESS_ON    1
+#define HB_EGRESS_VOTES 2
 int  hb_set_egress(hb_handle* h, int on);
+/* The mode in force: 0 (off), HB_EGRESS_ON, or HB_EGRESS_ON | HB_EGRESS_VOTES;
+ * HB_EINVAL for a NULL handle.  Vote mode is an addition inside ABI 8 (every
+ * value of `on` used before keeps its meaning), so the version number does not
+ * tell whether a library knows the bit: one that lacks this function does not
+ * (it takes any non-zero `on` as HB_EGRESS_ON and makes no vote record). */
+int  hb_egress_mode(hb_handle* h);
+/* A vote record whose LogTerm the device cannot tell: info carries this flag
+ * and log_term = 0; the host builds the message from its event as before. */
+#define HB_OUT_HOST     0x400u
 /* One record per HB_EV_RESP / HB_EV_HEARTBEAT event of the last step or tick
  * (since hb_set_egress), in chunk order then word order of hb_events_device:
  * a group's records are in the order the reference appended the messages to
@@ -570,19 +590,30 @@ int  hb_set_egress(hb_handle* h, int on);
  * RejectHint = its lastIndex at the send; `to` = the node id hb_load_peers
  * gave the slot (HB_EINVAL if no peer row was ever loaded), or to_ref =
  * HB_REF_OTHER and to = 0 for a sender outside prs (the host knows its id).
- * Messages with entries, a snapshot or a LogTerm (HB_EV_APP / _SNAP / _VOTE,
- * HB_EV_PROP_FWD) make no record: the host builds them as before.  self_id
- * is this node's id; a record holds no sender (hb_encode writes m.From), so
- * hb_egress only takes it for symmetry with hb_encode.
+ * Vote mode: also one MsgVote record per HB_EV_VOTE event (one per slot of a
+ * broadcast word's mask, in slot order): m.Term = the Term after
+ * becomeCandidate, m.Index = the event's x, m.LogTerm = raftLog.lastTerm() at
+ * the send, replayed from the pre-step column: the group's own appends
+ * (HB_EV_LAST) set it to the Term of that point.  It is unknown, and the record
+ * flagged HB_OUT_HOST, only when the group appended a leader's entries or
+ * restored a snapshot earlier in the same call (the events carry no entry
+ * terms), or when its last index lay below the current-term run and its term
+ * runs were never loaded (hb_load_term_runs); a campaign from hb_tick never is.
+ * Messages with entries or a snapshot (HB_EV_APP / _SNAP, HB_EV_PROP_FWD), and
+ * without vote mode HB_EV_VOTE, make no record: the host builds them as
+ * before.  self_id is this node's id; a record holds no sender (hb_encode
+ * writes m.From), so hb_egress only takes it for symmetry with hb_encode.
  * *count (device-readable: device memory or hb_alloc_pinned memory) = the
- * number of records; when it exceeds cap only the first cap are written and
- * the caller calls again (the events stay valid until the next step). */
+ * number of records; when it exceeds cap only the first cap are written (a cut
+ * may fall between two records of one broadcast word) and the caller calls
+ * again (the events stay valid until the next step). */
 int  hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t cap, uint64_t* count);
 /* Record i (m.From = self_id) becomes bytes[off[i], off[i+1]), packed densely
  * in record order, 28 to 91 bytes each; off[n] and *total = the byte count.
  * n = *n_dev (device-readable like *total, e.g. hb_egress's count, clamped to
  * cap; NULL = cap).  status[i] = HB_WIRE_OK, or HB_WIRE_HOST with length 0 for
- * a record whose to_ref is HB_REF_OTHER.  When *total > bytes_cap no byte is
+ * a record whose to_ref is HB_REF_OTHER or whose info carries HB_OUT_HOST.
+ * When *total > bytes_cap no byte is
  * written (off, status and total are): call again with a larger buffer, 91 x n
  * always suffices.  HB_EINVAL before any device work: a NULL handle or array,
  * cap > max_batch x (max_replicas + 4), cap x 91 >= 2^32. */
@@ -614,6 +645,7 @@ int  hb_set_egress_peers(hb_handle* h, const uint64_t* ids, uint32_t n);
  * src[j] (optional, may be NULL) = the index in `in` of output record j.
  * Bin of a record: to_ref == HB_REF_OTHER -> "other"; else the b with ids[b] == to
  * (all 64 bits); no such b -> "other".
+ * A record flagged HB_OUT_HOST moves like any other: binned by its `to`, info unchanged.
  * Records of `out` (and src) at and past n are not written; `in` is not written.
  * n = 0 and cap = 0 are legal: bin_off is then all zeros.
  * HB_EINVAL before any device work: NULL handle / batch / array / bin_off, no table set,

@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """Micro-benchmark of wire egress: hb_egress + hb_encode (not product code).
 
-Two workloads on a handle of 1,048,576 groups x 3:
+Workloads on a handle of 1,048,576 groups x 3:
 
   follow  the follow workload of bench.py (synth.follow_groups / follow_batch:
           every group receives its leader's MsgApp and MsgHeartbeat), so a step
           leaves one MsgAppResp and one MsgHeartbeatResp per group to send;
   tick    one MultiNode.Tick with half the groups leaders beating
-          (HeartbeatTick 1): two MsgHeartbeat per leader.
+          (HeartbeatTick 1): two MsgHeartbeat per leader;
+  campaign  (--workload campaign, after the two above in the same process) one
+          MultiNode.Tick in which every group's election timeout fires, vote
+          mode on (hb_set_egress bit HB_EGRESS_VOTES): two MsgVote per group,
+          every group one EVC_VBCAST word.
 
 Per workload: the step (or tick) runs once with egress on, then hb_egress +
 hb_encode (chained through the device-resident count, no host sync between
@@ -16,15 +20,17 @@ bracketed by HIP events on the handle's stream.  Reported: median [min, max]
 in microseconds, the records and wire bytes, and the bytes of a model with the
 rate it implies at the median:
 
-  events read (8 B per word) + the snapshot (16 B per group) + the peer id
-  (8 B per record) + the record written and read back (56 + 52 B) + the wire
-  bytes written.
+  events read (8 B per word) + the snapshot (16 B per group, 24 B in vote
+  mode: lterm0) + the peer id (8 B per record) + the record written and read
+  back (56 + 52 B) + the wire bytes written.
 
 (The model counts the event words once; hb_egress's count pass reads them a
 second time.)  The cost of the pre-step snapshot is measured beside it: K
-back-to-back steps of the follow and the cfg2 workload with egress off and on.
+back-to-back steps of the follow and the cfg2 workload with egress off, on
+(mode 1) and on with votes (mode 3: the third column), in the same run.
 
   python tools/microbench/egress_bench.py [--out profiles/egress_bench.json]
+  python tools/microbench/egress_bench.py --workload campaign [--out profiles/egress_vote_bench.json]
 """
 import argparse
 import json
@@ -85,11 +91,11 @@ def timed(torch, stream, eng, sink, reps):
     return us
 
 
-def report(name, eng, sink, us, reps):
+def report(name, eng, sink, us, reps, snap=16):
     _, counts = eng.event_words()
     words = int(counts.sum())
     records, wire = int(sink.count.item()), int(sink.total.item())
-    model = 8 * words + 16 * G + 8 * records + (REC_WRITE + REC_READ) * records + wire
+    model = 8 * words + snap * G + 8 * records + (REC_WRITE + REC_READ) * records + wire
     r = dict(case=name, groups=G, replicas=N, reps=reps, event_words=words, records=records, wire_bytes=wire,
              event_us=dict(median=float(np.median(us)), min=float(np.min(us)), max=float(np.max(us))),
              model_bytes=int(model), model_GBps_at_median=float(model / np.median(us) / 1e3),
@@ -116,6 +122,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--workload", choices=("egress", "campaign"), default="egress")
     args = ap.parse_args()
     import torch
     stream = torch.cuda.Stream()
@@ -131,7 +138,7 @@ def main():
         eng.load_peers(peers())
         d = {k: dv(torch, b[k]) for k in ("group", "info", "term", "hint", "eoff", "eterm", "index", "commit")}
         i_inc = dv(torch, ((b["info"] & 0xF) == abi.HB_MSG_APP).astype(np.uint64))
-        total_steps = 2 * (5 + args.steps) + 1
+        total_steps = 3 * (5 + args.steps) + 1
 
         def follow(k):
             eng.step(d["group"], d["info"], d["term"], d["index"] + i_inc * k, d["hint"], None, host=False,
@@ -139,8 +146,11 @@ def main():
         off_ms = steps_ms(torch, stream, follow, args.steps)
         eng.set_egress(True)
         on_ms = steps_ms(torch, stream, lambda k: follow(5 + args.steps + k), args.steps)
+        eng.set_egress(True, votes=True)
+        votes_ms = steps_ms(torch, stream, lambda k: follow(2 * (5 + args.steps) + k), args.steps)
+        eng.set_egress(True)
         snapshot.append(dict(workload="follow", steps=args.steps, ms_per_step_egress_off=off_ms,
-                             ms_per_step_egress_on=on_ms))
+                             ms_per_step_egress_on=on_ms, ms_per_step_egress_votes=votes_ms))
         follow(total_steps - 1)
         sink = Sink(torch, nmsg)
         us = timed(torch, stream, eng, sink, args.reps)
@@ -161,8 +171,10 @@ def main():
         off_ms = steps_ms(torch, stream, cfg2, args.steps)
         eng.set_egress(True)
         on_ms = steps_ms(torch, stream, lambda k: cfg2(5 + args.steps + k), args.steps)
+        eng.set_egress(True, votes=True)
+        votes_ms = steps_ms(torch, stream, lambda k: cfg2(2 * (5 + args.steps) + k), args.steps)
         snapshot.append(dict(workload="cfg2", steps=args.steps, ms_per_step_egress_off=off_ms,
-                             ms_per_step_egress_on=on_ms))
+                             ms_per_step_egress_on=on_ms, ms_per_step_egress_votes=votes_ms))
         print(json.dumps(snapshot), flush=True)
         eng.close()
         del x
@@ -185,6 +197,28 @@ def main():
         results.append(report("tick: half the groups leaders, two MsgHeartbeat each", eng, sink, us, args.reps))
         assert int(sink.count.item()) == (N - 1) * (G // 2)
         eng.close()
+        del sink
+        # ---- campaign: every group's election timeout fires, vote mode ----------------
+        if args.workload == "campaign":
+            g, _ = synth.follow_groups(G, N, seed=0x5EED0006, with_runs=False)
+            eng = Engine(G, max_replicas=N, max_inflight=W, max_batch=G, stream=stream)
+            eng.load_groups(g)
+            eng.load_peers(peers())
+            t["elapsed"] = 20  # past every randomized timeout (ElectionTick 10)
+            eng.load_timers(t)
+            eng.set_rand(np.random.default_rng(seed).integers(0, 1 << 63, 64, dtype=np.uint64))
+            eng.set_egress(True, votes=True)
+            eng.tick()
+            sink = Sink(torch, 2 * G)
+            us = timed(torch, stream, eng, sink, args.reps)
+            results.append(report("campaign: every group times out, two MsgVote each (vote mode)", eng, sink, us,
+                                  args.reps, snap=24))
+            info = sink.out["info"].cpu().numpy().view(np.uint32)
+            assert int(sink.count.item()) == (N - 1) * G and ((info & 0xF) == abi.HB_MSG_VOTE).all()
+            assert not (info & abi.HB_OUT_HOST).any() and (sink.status.cpu().numpy() == abi.HB_WIRE_OK).all()
+            words, _ = eng.event_words()
+            assert int(((words & np.uint64(0xF)) == abi.HB_EVW_VBCAST).sum()) == G
+            eng.close()
     out = dict(bench="hb_egress + hb_encode", results=results, snapshot_cost=snapshot)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
