@@ -27,6 +27,9 @@ HB_INFO_VOTED = 0x200
 HB_OUT_HOST = 0x400      # hb_out_batch info: a MsgVote record the host builds (LogTerm unknown)
 HB_EGRESS_ON = 1
 HB_EGRESS_VOTES = 2       # hb_set_egress bit: MsgVote records
+HB_EGRESS_APPS = 4        # hb_set_egress bit: MsgApp records
+HB_OUT_ENTS = 0x800       # hb_out_batch info: a MsgApp record that carries entries (index, hint]
+HB_WIRE_SPLICE = 0x80     # hb_encode status bit: the low 7 bits are the prefix length
 HB_ENT_MAX_DATA = 0x3FFFFFFF
 
 # StateType raft/raft.go:35-39

@@ -3585,10 +3585,13 @@ constexpr uint32_t ENC_SMALL_THREADS = 512;
 constexpr uint32_t ENC_SMALL_MAX = 16384;  // the small-step rule: one workgroup, one launch
 constexpr uint32_t ENC_WIN = 64 * WO_MAX + 16;  // a wave's span plus the 16-byte phase of its first byte
 static_assert(ENC_WIN % 16 == 0, "the window is read back as uint4");
+static_assert(WO_PREFIX_MAX + 1 + WO_VARINT_MAX + WO_SNAP_LEN + 4 <= WO_MAX && WO_PREFIX_MAX < HB_WIRE_SPLICE,
+              "a split record (HB_OUT_ENTS) is a payload-free record: WO_MAX and the window hold");
 
 struct EncRec {
   uint32_t type;
   bool reject, host;
+  bool ents;  // HB_OUT_ENTS: the split form (hint is the last entry's index, not a RejectHint)
   uint64_t to, term, log_term, index, commit, hint;
 };
 __device__ __forceinline__ uint64_t enc_n(const EncodeArgs& a) {
@@ -3596,9 +3599,11 @@ __device__ __forceinline__ uint64_t enc_n(const EncodeArgs& a) {
   return n < a.cap ? n : a.cap;
 }
 // record i and its encoded length (0: past the end, HB_REF_OTHER: the host knows the id, or
-// HB_OUT_HOST: a MsgVote whose LogTerm the replay could not tell)
+// HB_OUT_HOST: a MsgVote or MsgApp the replay could not complete).  A record with HB_OUT_ENTS
+// is the entry-free message (Reject = 0, RejectHint = 0): prefix ‖ suffix, wo_prefix_len.
 __device__ __forceinline__ uint32_t enc_load(const EncodeArgs& a, uint64_t i, uint64_t n, EncRec* r) {
   r->host = false;
+  r->ents = false;
   if (i >= n) return 0;
   const uint32_t info = a.info[i];
   r->type = info & 0xF;
@@ -3611,6 +3616,11 @@ __device__ __forceinline__ uint32_t enc_load(const EncodeArgs& a, uint64_t i, ui
   r->index = a.index[i];
   r->commit = a.commit[i];
   r->hint = a.hint[i];
+  r->ents = (info & HB_OUT_ENTS) != 0;
+  if (r->ents) {
+    r->reject = false;
+    r->hint = 0;
+  }
   return wo_size(r->type, r->to, a.self_id, r->term, r->log_term, r->index, r->commit, r->reject, r->hint);
 }
 
@@ -3627,7 +3637,10 @@ __device__ __forceinline__ uint32_t enc_tile(const EncodeArgs& a, uint64_t i0, u
   const uint64_t p = base + ex;
   if (i < n) {
     a.off[i] = p;
-    a.status[i] = r.host ? (uint8_t)HB_WIRE_HOST : (uint8_t)HB_WIRE_OK;
+    uint8_t st = r.host ? (uint8_t)HB_WIRE_HOST : (uint8_t)HB_WIRE_OK;
+    if (r.ents)
+      st = (uint8_t)(HB_WIRE_SPLICE | wo_prefix_len(r.type, r.to, a.self_id, r.term, r.log_term, r.index));
+    a.status[i] = st;
   }
   if (!write) return tot;
   const uint64_t lo = __shfl(p, 0), hi = __shfl(p + sz, 63);  // the wave's span
@@ -3711,19 +3724,25 @@ __global__ void __launch_bounds__(ENC_SMALL_THREADS) k_enc_small(EncodeArgs a) {
 // words of a chunk interleave the partition's groups in emission order, and a
 // record's place in the output is fixed by its word's place in the chunk: a
 // per-word record count (1 for a response or a heartbeat, in vote mode 1 for
-// a vote and the mask's population for a vote broadcast; the engine emits
+// a vote and the mask's population for a vote broadcast, in append mode the
+// same for HB_EV_APP and EVC_BCAST; the engine emits
 // nothing for a group after its HB_EV_FAULT), a block scan per tile, a
 // running base per chunk, chunk bases from a scan over the chunks.  A chunk
 // goes through LDS in tiles of EG_TILE words; every lane then walks the tile's
 // group bytes (16 per LDS broadcast read) and consumes its own group's words
-// in order, carrying (term, last, pend) in registers across tiles and chunks.
+// in order, carrying (term, last, pend) in registers across tiles and chunks
+// (vote mode: lt too; append mode: lt, cm, bl, blt).
 struct EgressArgs {
   const uint64_t* ev;
   const uint64_t* ev_off;
   const uint32_t* ev_counts;
   uint32_t nc, G;
   const uint64_t *term0, *last0, *peer;
-  const uint64_t* lterm0;  // [G] vote mode: lastTerm before the step, or HB_LT_UNKNOWN (else null)
+  const uint64_t* lterm0;  // [G] vote / append mode: lastTerm before the step, or HB_LT_UNKNOWN (else null)
+  // append mode (else null): committed before the step, and the boundary pair: the index just
+  // below the current-term run and its term (HB_LT_UNKNOWN: not known to the device)
+  const uint64_t *commit0, *bl0, *blt0;
+  uint64_t max_msg_size;
   uint32_t* ccnt;    // [nc] records per chunk
   uint64_t* cbase;   // [nc + 1] their exclusive scan, then the total
   uint64_t cap;
@@ -3738,23 +3757,29 @@ constexpr uint32_t EG_SMALL = 1024;  // chunks the one-workgroup count + scan ta
 static_assert(EG_PER == 8, "a lane's group bytes of a tile are one 8-byte LDS store");
 
 // The records a word makes.  VOTES (hb_set_egress bit HB_EGRESS_VOTES): campaign's MsgVotes too,
-// one for an HB_EV_VOTE word and one per slot of an EVC_VBCAST word's mask.
-template <bool VOTES>
+// one for an HB_EV_VOTE word and one per slot of an EVC_VBCAST word's mask.  APPS (bit
+// HB_EGRESS_APPS): sendAppend's MsgApps too, one for an HB_EV_APP word and one per slot of an
+// EVC_BCAST word's mask.
+template <bool VOTES, bool APPS>
 __device__ __forceinline__ uint32_t eg_record(uint64_t w) {
   const uint32_t t = (uint32_t)w & 0xF;
+  if (APPS) {
+    if (t == EVC_BCAST) return (uint32_t)__popc((uint32_t)(w >> 4) & 0x7Fu);
+    if (t == HB_EV_APP) return 1u;
+  }
   if (VOTES) {
     if (t == EVC_VBCAST) return (uint32_t)__popc((uint32_t)(w >> 4) & 0x7Fu);
     if (t == HB_EV_VOTE) return 1u;
   }
   return (t == HB_EV_RESP || t == HB_EV_HEARTBEAT) ? 1u : 0u;
 }
-template <bool VOTES>
+template <bool VOTES, bool APPS>
 __global__ void __launch_bounds__(256) k_eg_count(EgressArgs a) {
   __shared__ uint32_t sh16[16];
   const uint32_t c = blockIdx.x, n = a.ev_counts[c];
   const uint64_t* src = a.ev + a.ev_off[c];
   uint32_t k = 0;
-  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) k += eg_record<VOTES>(src[i]);
+  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) k += eg_record<VOTES, APPS>(src[i]);
   uint32_t tot;
   (void)block_excl_scan(k, sh16, &tot);
   if (threadIdx.x == 0) a.ccnt[c] = tot;
@@ -3776,7 +3801,7 @@ __global__ void __launch_bounds__(1024) k_eg_scan(EgressArgs a) {
   }
 }
 // Count and scan in one workgroup when the chunks are few: a wave per chunk counts.
-template <bool VOTES>
+template <bool VOTES, bool APPS>
 __global__ void __launch_bounds__(1024) k_eg_small(EgressArgs a) {
   __shared__ uint32_t sh16[16];
   __shared__ uint32_t s_cnt[EG_SMALL];
@@ -3785,7 +3810,7 @@ __global__ void __launch_bounds__(1024) k_eg_small(EgressArgs a) {
     const uint32_t n = a.ev_counts[c];
     const uint64_t* src = a.ev + a.ev_off[c];
     uint32_t k = 0;
-    for (uint32_t i = lane; i < n; i += 64) k += eg_record<VOTES>(src[i]);
+    for (uint32_t i = lane; i < n; i += 64) k += eg_record<VOTES, APPS>(src[i]);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) k += __shfl_xor(k, d);
     if (lane == 0) s_cnt[c] = k;
@@ -3801,7 +3826,7 @@ __global__ void __launch_bounds__(1024) k_eg_small(EgressArgs a) {
   }
 }
 
-template <bool VOTES>
+template <bool VOTES, bool APPS>
 __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
   __shared__ uint64_t s_w[EG_TILE];
   __shared__ uint32_t s_pos[EG_TILE];
@@ -3811,7 +3836,16 @@ __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
   const bool live = g < a.G;
   uint64_t term = live ? a.term0[g] : 0ull, last = live ? a.last0[g] : 0ull;
   uint64_t lt = 0;  // VOTES: raftLog.lastTerm() at this point of the replay, or HB_LT_UNKNOWN
-  if (VOTES) lt = live ? a.lterm0[g] : 0ull;
+  if (VOTES || APPS) lt = live ? a.lterm0[g] : 0ull;
+  // APPS: raftLog.committed, and the boundary pair (the index just below the current-term run,
+  // HB_NO_INDEX: unknown; its term, or HB_LT_UNKNOWN) at this point of the replay
+  uint64_t cm = 0, bl = HB_NO_INDEX, blt = HB_LT_UNKNOWN;
+  if (APPS && live) {
+    cm = a.commit0[g];
+    bl = a.bl0[g];
+    blt = a.blt0[g];
+  }
+  bool cm_known = true;
   bool pend = false, dead = false;
   const uint32_t pat = tid * 0x01010101u;
   for (uint32_t c = 2 * part; c < 2 * part + 2; ++c) {
@@ -3827,7 +3861,7 @@ __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
       for (uint32_t j = 0; j < EG_PER; ++j) {
         const uint32_t li = tid * EG_PER + j;
         w[j] = li < m ? src[t0 + li] : (uint64_t)EVC_CONT;
-        k += eg_record<VOTES>(w[j]);
+        k += eg_record<VOTES, APPS>(w[j]);
       }
       uint32_t tot;
       uint32_t pos = block_excl_scan(k, sh16, &tot);
@@ -3837,7 +3871,7 @@ __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
         const uint32_t li = tid * EG_PER + j;
         s_w[li] = w[j];
         s_pos[li] = pos;
-        pos += eg_record<VOTES>(w[j]);
+        pos += eg_record<VOTES, APPS>(w[j]);
         const uint32_t kb = (uint32_t)(w[j] >> 16) & 0xFF;
         if (j < 4) klo |= kb << (8 * j);
         else khi |= kb << (8 * (j - 4));
@@ -3865,16 +3899,57 @@ __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
               const uint64_t cw = li + 1 < m ? s_w[li + 1] : (t0 + li + 1 < n ? src[t0 + li + 1] : 0ull);
               xv |= (cw >> 4) << 40;
             }
-            if (type == HB_EV_TERM) term = xv;
-            else if (type == HB_EV_LAST) {
+            if (type == HB_EV_TERM) {
+              term = xv;
+              if (APPS) {  // reset: the current-term run is empty, the log is unchanged
+                bl = pend ? HB_NO_INDEX : last;
+                blt = lt;
+              }
+            } else if (APPS && type == HB_EV_COMMIT) {
+              cm = xv;
+              cm_known = true;
+            } else if (type == HB_EV_LAST) {
               last = xv;
-              if (VOTES) lt = term;  // appendEntry: the group's own entries carry its Term
+              if (VOTES || APPS) lt = term;  // appendEntry: the group's own entries carry its Term
             } else if (type == HB_EV_FOLLOW) {
               const bool app = aux == HB_FOLLOW_APPEND || aux == HB_FOLLOW_RESTORE;
               pend |= app;
-              if (VOTES && app) lt = HB_LT_UNKNOWN;  // the events hold no terms of a leader's entries
+              if ((VOTES || APPS) && app) lt = HB_LT_UNKNOWN;  // the events hold no terms of a leader's entries
+              if (APPS && app) {  // ... nor where the current-term run now starts
+                bl = HB_NO_INDEX;
+                blt = HB_LT_UNKNOWN;
+                cm_known = false;  // until the next HB_EV_COMMIT
+              }
             } else if (type == HB_EV_FAULT) dead = true;
-            else if (VOTES && (type == HB_EV_VOTE || type == EVC_VBCAST)) {
+            else if (APPS && (type == HB_EV_APP || type == EVC_BCAST)) {
+              // sendAppend's MsgApp (raft/raft.go:261-281): one record per slot, in slot order.
+              // LogTerm: the Term when the aux bit says so, the boundary's term for a send at the
+              // boundary; anything the replay cannot prove leaves the record to the host.
+              const bool at_bl = bl != HB_NO_INDEX && xv == bl && blt != HB_LT_UNKNOWN;
+              bool host = !((aux & 1u) || at_bl) || !cm_known;
+              const uint64_t lterm = (aux & 1u) ? term : blt;
+              const bool ents = xv < last;  // entries (x, L]
+              uint64_t L = 0;
+              if (ents) {
+                if (a.max_msg_size == HB_NO_LIMIT) L = last;
+                else if (a.max_msg_size == 0) L = xv + 1;
+                else host = true;  // limitSize's cut: no event carries it
+              }
+              const uint32_t flags = host ? (uint32_t)HB_OUT_HOST : (ents ? (uint32_t)HB_OUT_ENTS : 0u);
+              uint32_t mask = type == EVC_BCAST ? to : 1u << (to <= HB_REF_SLOT_MAX ? to : 7u);
+              for (uint64_t o = run + s_pos[li]; mask && o < a.cap; mask &= mask - 1, ++o) {
+                const uint32_t s = (uint32_t)__ffs(mask) - 1;
+                const bool slot = s <= HB_REF_SLOT_MAX;  // (no lane sends a MsgApp outside prs)
+                a.o_group[o] = g;
+                a.o_info[o] = HB_INFO(HB_MSG_APP, slot ? s : (uint32_t)HB_REF_OTHER, false) | flags;
+                a.o_to[o] = slot ? a.peer[(size_t)g * HB_PEER_ROW + s] : 0ull;
+                a.o_term[o] = term;
+                a.o_log_term[o] = host ? 0ull : lterm;
+                a.o_index[o] = xv;
+                a.o_commit[o] = host ? 0ull : cm;
+                a.o_hint[o] = host ? 0ull : L;
+              }
+            } else if (VOTES && (type == HB_EV_VOTE || type == EVC_VBCAST)) {
               // campaign's MsgVote (raft/raft.go:429-443): one record per slot, in slot order; a
               // LogTerm the replay cannot tell leaves the record to the host (HB_OUT_HOST)
               const bool known = lt != HB_LT_UNKNOWN;
@@ -3944,8 +4019,10 @@ struct SnapArgs {
   const uint64_t *term, *last;
   uint64_t *term0, *last0;
   uint32_t G;
-  const uint64_t *tfirst, *trx, *trc;  // VOTES only
+  const uint64_t *tfirst, *trx, *trc;  // VOTES / append mode only
   uint64_t* lterm0;
+  const uint64_t *commit, *first;  // append mode only
+  uint64_t *commit0, *bl0, *blt0;
 };
 __device__ __forceinline__ uint64_t eg_last_term(const SnapArgs& a, uint32_t g, uint64_t term, uint64_t last) {
   const uint64_t tf = a.tfirst[g];
@@ -3988,6 +4065,48 @@ __global__ void __launch_bounds__(256) k_eg_snap(SnapArgs a) {
     a.last0[i] = l;
     a.lterm0[i] = eg_last_term(a, i, t, l);
   }
+}
+// Append mode (hb_set_egress bit HB_EGRESS_APPS): term0, last0, lterm0 as above, commit0, and the
+// boundary pair: bl0 = the index just below the current-term run (tfirst - 1; with no such run
+// the log's last index, where a run would start) and blt0 = its term as Lane::fterm(bl0) gives
+// it, HB_LT_UNKNOWN when the ring does not reach or bl0 lies below the log (first - 1 is the
+// lowest index with a term).  One group per lane: a group with a current-term run reads its
+// ring for blt0, one without reads it once (blt0 = lterm0).
+__global__ void __launch_bounds__(256) k_eg_snap_app(SnapArgs a) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= a.G) return;
+  const uint64_t t = a.term[g], l = a.last[g], tf = a.tfirst[g];
+  a.term0[g] = t;
+  a.last0[g] = l;
+  a.commit0[g] = a.commit[g];
+  const bool run = tf != HB_NO_INDEX;
+  const uint64_t b = run ? tf - 1 : l;  // (tfirst = 0 gives HB_NO_INDEX: below the log)
+  uint64_t lt = HB_LT_UNKNOWN, bt = HB_LT_UNKNOWN;
+  if (run && l >= tf) lt = t;
+  if (lt == HB_LT_UNKNOWN || b + 1 >= a.first[g]) {
+    const uint64_t x = a.trx[g], c = a.trc[g];
+    Runs r;
+    r.R = lx_base(x);
+    r.mask = lx_cap(x) - 1;
+    r.n = (uint32_t)c;
+    r.h = (uint32_t)(c >> 32);
+    if (lt == HB_LT_UNKNOWN) {
+      bool ok = true;
+      const uint64_t v = r.find(l, &ok);
+      if (ok) lt = v;
+    }
+    if (!run) {
+      bt = lt;
+    } else if (b + 1 >= a.first[g]) {
+      bool ok = true;
+      const uint64_t v = r.find(b, &ok);
+      if (ok) bt = v;
+    }
+  }
+  if (b + 1 < a.first[g]) bt = HB_LT_UNKNOWN;
+  a.lterm0[g] = lt;
+  a.bl0[g] = b;
+  a.blt0[g] = bt;
 }
 
 // ============================================================================
@@ -4523,6 +4642,10 @@ struct hb_handle {
   bool eg_stepped = false;        // a step or tick has run since hb_set_egress(on)
   bool eg_votes = false;          // HB_EGRESS_VOTES: MsgVote records, the lterm0 column
   uint64_t* lterm0 = nullptr;     // [G] raftLog.lastTerm() before the last step / tick, or HB_LT_UNKNOWN
+  bool eg_apps = false;           // HB_EGRESS_APPS: MsgApp records; lterm0 and the three columns below
+  uint64_t* eg_commit0 = nullptr; // [G] raftLog.committed before it (commit0 below is the step's own)
+  uint64_t* bl0 = nullptr;        // [G] the index just below the current-term run before it
+  uint64_t* blt0 = nullptr;       // [G] that index's term, or HB_LT_UNKNOWN
   uint64_t* term0 = nullptr;      // [G] the term column before the last step / tick
   uint64_t* last0 = nullptr;      // [G] the last column before it
   uint32_t* eg_cnt = nullptr;     // [2 NB] records per chunk
@@ -4686,7 +4809,8 @@ uint32_t apply_grid_for(uint32_t NBK, uint32_t sl, uint32_t NB) {
 uint32_t apply_grid(const hb_handle* h) { return h->agrid; }
 
 // hb_set_egress: the group's Term and lastIndex before the step (one launch, 32 B per group moved;
-// vote mode: lastTerm too, 16 B per group more and a ring lookup for a last index below the current-term run)
+// vote mode: lastTerm too, 16 B per group more and a ring lookup for a last index below the current-term run;
+// append mode: committed and the boundary pair as well, k_eg_snap_app)
 void egress_snapshot(hb_handle* h, hipStream_t st) {
   SnapArgs a;
   a.term = h->st.term;
@@ -4698,7 +4822,13 @@ void egress_snapshot(hb_handle* h, hipStream_t st) {
   a.trx = h->st.trx;
   a.trc = h->st.trc;
   a.lterm0 = h->lterm0;
-  if (h->eg_votes) hipLaunchKernelGGL(k_eg_snap<true>, dim3((h->G + 511) / 512), dim3(256), 0, st, a);
+  a.commit = h->st.commit;
+  a.first = h->st.first;
+  a.commit0 = h->eg_commit0;
+  a.bl0 = h->bl0;
+  a.blt0 = h->blt0;
+  if (h->eg_apps) hipLaunchKernelGGL(k_eg_snap_app, dim3((h->G + 255) / 256), dim3(256), 0, st, a);
+  else if (h->eg_votes) hipLaunchKernelGGL(k_eg_snap<true>, dim3((h->G + 511) / 512), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(k_eg_snap<false>, dim3((h->G + 511) / 512), dim3(256), 0, st, a);
   h->eg_stepped = true;
 }
@@ -5003,7 +5133,8 @@ int hb_destroy(hb_handle* h) {
   if (h->peer) (void)hipFree(h->peer);
   if (h->dec_q) (void)hipFree(h->dec_q);
   if (h->dec_qn) (void)hipFree(h->dec_qn);
-  for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->lterm0, (void*)h->eg_cnt, (void*)h->eg_base, (void*)h->enc_sum,
+  for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->lterm0, (void*)h->eg_commit0, (void*)h->bl0, (void*)h->blt0,
+                  (void*)h->eg_cnt, (void*)h->eg_base, (void*)h->enc_sum,
                   (void*)h->enc_base, (void*)h->bin_table, (void*)h->bin_key, (void*)h->bin_hist})
     if (p) (void)hipFree(p);
   if (h->in_ready) (void)hipEventDestroy(h->in_ready);
@@ -5929,57 +6060,80 @@ int hb_events_to_host(hb_handle* h, uint64_t* words, uint64_t cap, uint32_t* cou
 }
 
 // ---- wire egress ---------------------------------------------------------------
+// the snapshot columns of a mode: lterm0 in vote and append mode, commit0 / bl0 / blt0 in append mode
+static void egress_free_cols(hb_handle* h, bool lt, bool apps) {
+  if (lt && h->lterm0) (void)hipFree(h->lterm0);
+  if (lt) h->lterm0 = nullptr;
+  if (!apps) return;
+  for (void* p : {(void*)h->eg_commit0, (void*)h->bl0, (void*)h->blt0})
+    if (p) (void)hipFree(p);
+  h->eg_commit0 = h->bl0 = h->blt0 = nullptr;
+}
+static bool egress_alloc_cols(hb_handle* h, bool lt, bool apps) {
+  const size_t G = h->G;
+  if (lt && !h->lterm0 && hipMalloc(&h->lterm0, G * 8) != hipSuccess) {
+    h->lterm0 = nullptr;
+    return false;
+  }
+  if (apps && !h->eg_commit0 &&
+      (hipMalloc(&h->eg_commit0, G * 8) != hipSuccess || hipMalloc(&h->bl0, G * 8) != hipSuccess ||
+       hipMalloc(&h->blt0, G * 8) != hipSuccess))
+    return false;
+  return true;
+}
 int hb_set_egress(hb_handle* h, int on) {
   if (!h) return HB_EINVAL;
   DeviceGuard guard(h->device);
-  const bool votes = on && (on & HB_EGRESS_VOTES);
-  if (h->egress && (!on || votes != h->eg_votes))
+  const bool votes = on && (on & HB_EGRESS_VOTES), apps = on && (on & HB_EGRESS_APPS);
+  if (h->egress && (!on || votes != h->eg_votes || apps != h->eg_apps))
     HB_CHECK(hipStreamSynchronize(h->stream));  // an hb_egress may still read the columns
   if (!on) {
     if (!h->egress) return HB_OK;
-    for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->lterm0, (void*)h->eg_cnt, (void*)h->eg_base})
+    for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->eg_cnt, (void*)h->eg_base})
       if (p) (void)hipFree(p);
-    h->term0 = h->last0 = h->lterm0 = h->eg_base = nullptr;
+    egress_free_cols(h, true, true);
+    h->term0 = h->last0 = h->eg_base = nullptr;
     h->eg_cnt = nullptr;
-    h->egress = h->eg_votes = false;
+    h->egress = h->eg_votes = h->eg_apps = false;
     return HB_OK;
   }
   const size_t G = h->G, nc = 2 * (size_t)h->NB;
   if (h->egress) {
-    if (votes == h->eg_votes) return HB_OK;
+    if (votes == h->eg_votes && apps == h->eg_apps) return HB_OK;
     // the mode changes: the step before this call has no matching snapshot
-    if (votes) {
-      if (hipMalloc(&h->lterm0, G * 8) != hipSuccess) {
-        h->lterm0 = nullptr;
-        return HB_ENOMEM;
-      }
-    } else {
-      (void)hipFree(h->lterm0);
-      h->lterm0 = nullptr;
-    }
-    h->eg_votes = votes;
     h->eg_stepped = false;
+    if (!egress_alloc_cols(h, votes || apps, apps)) {  // (the mode in force stays; nothing new is kept)
+      egress_free_cols(h, !(h->eg_votes || h->eg_apps), !h->eg_apps);
+      return HB_ENOMEM;
+    }
+    egress_free_cols(h, !(votes || apps), !apps);
+    h->eg_votes = votes;
+    h->eg_apps = apps;
     return HB_OK;
   }
   if (hipMalloc(&h->term0, G * 8) != hipSuccess || hipMalloc(&h->last0, G * 8) != hipSuccess ||
       hipMalloc(&h->eg_cnt, nc * 4) != hipSuccess || hipMalloc(&h->eg_base, (nc + 1) * 8) != hipSuccess ||
-      (votes && hipMalloc(&h->lterm0, G * 8) != hipSuccess)) {
-    for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->lterm0, (void*)h->eg_cnt, (void*)h->eg_base})
+      !egress_alloc_cols(h, votes || apps, apps)) {
+    for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->eg_cnt, (void*)h->eg_base})
       if (p) (void)hipFree(p);
-    h->term0 = h->last0 = h->lterm0 = h->eg_base = nullptr;
+    egress_free_cols(h, true, true);
+    h->term0 = h->last0 = h->eg_base = nullptr;
     h->eg_cnt = nullptr;
     return HB_ENOMEM;
   }
   h->egress = true;
   h->eg_votes = votes;
+  h->eg_apps = apps;
   h->eg_stepped = false;  // the step before this call has no snapshot: its events are not replayed
   return HB_OK;
 }
 
 int hb_egress_mode(hb_handle* h) {
   if (!h) return HB_EINVAL;
-  return h->egress ? (HB_EGRESS_ON | (h->eg_votes ? HB_EGRESS_VOTES : 0)) : 0;
+  return h->egress ? (HB_EGRESS_ON | (h->eg_votes ? HB_EGRESS_VOTES : 0) | (h->eg_apps ? HB_EGRESS_APPS : 0)) : 0;
 }
+
+int hb_egress_caps(void) { return HB_EGRESS_ON | HB_EGRESS_VOTES | HB_EGRESS_APPS; }
 
 int hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t cap, uint64_t* count) {
   (void)self_id;  // m.From: hb_encode writes it; the batch holds no sender
@@ -6005,6 +6159,10 @@ int hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t 
   ea.last0 = h->last0;
   ea.peer = h->peer;
   ea.lterm0 = h->lterm0;
+  ea.commit0 = h->eg_commit0;
+  ea.bl0 = h->bl0;
+  ea.blt0 = h->blt0;
+  ea.max_msg_size = h->max_msg_size;
   ea.ccnt = h->eg_cnt;
   ea.cbase = h->eg_base;
   ea.cap = cap;
@@ -6018,16 +6176,22 @@ int hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t 
   ea.o_commit = out->commit;
   ea.o_hint = out->hint;
   const bool small = ea.nc <= EG_SMALL && !h->no_small;
-  if (h->eg_votes) {
-    if (small) hipLaunchKernelGGL(k_eg_small<true>, dim3(1), dim3(1024), 0, h->stream, ea);
-    else hipLaunchKernelGGL(k_eg_count<true>, dim3(ea.nc), dim3(256), 0, h->stream, ea);
-  } else {
-    if (small) hipLaunchKernelGGL(k_eg_small<false>, dim3(1), dim3(1024), 0, h->stream, ea);
-    else hipLaunchKernelGGL(k_eg_count<false>, dim3(ea.nc), dim3(256), 0, h->stream, ea);
-  }
-  if (!small) hipLaunchKernelGGL(k_eg_scan, dim3(1), dim3(1024), 0, h->stream, ea);
-  if (h->eg_votes) hipLaunchKernelGGL(k_egress<true>, dim3(h->NB), dim3(PART), 0, h->stream, ea);
-  else hipLaunchKernelGGL(k_egress<false>, dim3(h->NB), dim3(PART), 0, h->stream, ea);
+  // (the instantiations without APPS are the ones a handle without the bit always ran)
+#define EG_LAUNCH(V, A)                                                                              \
+  do {                                                                                               \
+    if (small) hipLaunchKernelGGL((k_eg_small<V, A>), dim3(1), dim3(1024), 0, h->stream, ea);       \
+    else {                                                                                           \
+      hipLaunchKernelGGL((k_eg_count<V, A>), dim3(ea.nc), dim3(256), 0, h->stream, ea);             \
+      hipLaunchKernelGGL(k_eg_scan, dim3(1), dim3(1024), 0, h->stream, ea);                         \
+    }                                                                                                \
+    hipLaunchKernelGGL((k_egress<V, A>), dim3(h->NB), dim3(PART), 0, h->stream, ea);                \
+  } while (0)
+  if (h->eg_apps) {
+    if (h->eg_votes) EG_LAUNCH(true, true);
+    else EG_LAUNCH(false, true);
+  } else if (h->eg_votes) EG_LAUNCH(true, false);
+  else EG_LAUNCH(false, false);
+#undef EG_LAUNCH
   return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
 }
 

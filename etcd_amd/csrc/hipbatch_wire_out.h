@@ -8,6 +8,9 @@
 //   08 type | 10 to | 18 from | 20 term | 28 logTerm | 30 index | 40 commit |
 //   4a 08 12 06 0a 00 10 00 18 00 | 50 reject (00 / 01) | 58 rejectHint
 //
+// A MsgApp with entries is written in the split form (wo_prefix_len below): the
+// same bytes, and the place where the host splices the entries.
+//
 // Plain C++ with no HIP header and no intrinsic: the engine compiles it for
 // the device (hb_encode, hipbatch.hip) and tests/asan/wire_out_asan.cpp for the
 // host, under the sanitizers.
@@ -61,6 +64,20 @@ WO_HD inline uint32_t wo_size(uint32_t type, uint64_t to, uint64_t from, uint64_
          wo_varint_len(hint);
 }
 
+// The split form, for a MsgApp that carries entries.  MarshalTo writes the
+// entries (field 7: 3a, varint(Entry.Size()), Entry, once per entry) as one
+// contiguous run between field 6 (Index) and field 8 (Commit), and a MsgApp's
+// Reject and RejectHint are 0.  So the record is written as prefix ‖ suffix, the
+// bytes of the same message without entries, and the run goes in at the prefix's
+// end: wo_prefix_len is fields 1-6, at most 6 keys + the type + 5 varints.
+constexpr uint32_t WO_PREFIX_MAX = 6 + 1 + 5 * WO_VARINT_MAX;
+static_assert(WO_PREFIX_MAX == 57 && WO_PREFIX_MAX < 0x80, "a prefix length fits the low 7 bits of a status byte");
+WO_HD inline uint32_t wo_prefix_len(uint32_t type, uint64_t to, uint64_t from, uint64_t term, uint64_t log_term,
+                                    uint64_t index) {
+  return 6 + wo_varint_len(type) + wo_varint_len(to) + wo_varint_len(from) + wo_varint_len(term) +
+         wo_varint_len(log_term) + wo_varint_len(index);
+}
+
 // Message.MarshalTo into dst[0, wo_size(...)); returns the bytes written
 WO_HD inline uint32_t wo_write(uint8_t* dst, uint32_t type, uint64_t to, uint64_t from, uint64_t term,
                                uint64_t log_term, uint64_t index, uint64_t commit, bool reject, uint64_t hint) {
@@ -87,5 +104,18 @@ WO_HD inline uint32_t wo_write(uint8_t* dst, uint32_t type, uint64_t to, uint64_
   i = wo_put_varint(dst, i, hint);
   return i;
 }
+
+// Size and bytes of the split record: those of the entry-free message with Reject = 0 and
+// RejectHint = 0, whatever the record's hint column holds (there: the last entry's index).
+WO_HD inline uint32_t wo_size_split(uint32_t type, uint64_t to, uint64_t from, uint64_t term, uint64_t log_term,
+                                    uint64_t index, uint64_t commit) {
+  return wo_size(type, to, from, term, log_term, index, commit, false, 0);
+}
+WO_HD inline uint32_t wo_write_split(uint8_t* dst, uint32_t type, uint64_t to, uint64_t from, uint64_t term,
+                                     uint64_t log_term, uint64_t index, uint64_t commit) {
+  return wo_write(dst, type, to, from, term, log_term, index, commit, false, 0);
+}
+// the split record is a payload-free record: the bounds and hb_encode's LDS window hold
+static_assert(WO_PREFIX_MAX + 1 + WO_VARINT_MAX + WO_SNAP_LEN + 2 + 2 <= WO_MAX, "prefix + suffix within WO_MAX");
 
 }  // namespace hb

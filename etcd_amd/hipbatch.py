@@ -123,6 +123,7 @@ def lib():
                                 C.c_void_p]),
         "hb_set_egress": (C.c_int, [H, C.c_int]),
         "hb_egress_mode": (C.c_int, [H]),
+        "hb_egress_caps": (C.c_int, []),
         "hb_egress": (C.c_int, [H, C.c_uint64, P(abi.hb_out_batch), C.c_uint64, C.c_void_p]),
         "hb_encode": (C.c_int, [H, P(abi.hb_out_batch), C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -357,15 +358,18 @@ class Engine:
                                             C.byref(b), _ptr(status)))
 
     # ---- wire egress ---------------------------------------------------------------
-    def set_egress(self, on=True, votes=False):
+    def set_egress(self, on=True, votes=False, apps=False):
         """hb_set_egress: every later step / tick keeps the groups' Term and lastIndex
         from before it, which egress() needs; off frees them.  votes: vote mode
-        (HB_EGRESS_VOTES), the lastTerm column too and campaign's MsgVote records."""
-        mode = (abi.HB_EGRESS_ON | (abi.HB_EGRESS_VOTES if votes else 0)) if on else 0
+        (HB_EGRESS_VOTES), the lastTerm column too and campaign's MsgVote records.
+        apps: append mode (HB_EGRESS_APPS), the committed column and the boundary pair
+        too and sendAppend's MsgApp records (etcd_amd.splice completes those with entries)."""
+        mode = (abi.HB_EGRESS_ON | (abi.HB_EGRESS_VOTES if votes else 0) | (abi.HB_EGRESS_APPS if apps else 0)) \
+            if on else 0
         _check("hb_set_egress", lib().hb_set_egress(self.h, mode))
 
     def egress_mode(self):
-        """hb_egress_mode: 0, HB_EGRESS_ON, or HB_EGRESS_ON | HB_EGRESS_VOTES."""
+        """hb_egress_mode: 0, or HB_EGRESS_ON | any of HB_EGRESS_VOTES and HB_EGRESS_APPS."""
         m = lib().hb_egress_mode(self.h)
         if m < 0:
             raise HipBatchError("hb_egress_mode", m)

@@ -541,6 +541,8 @@ int  hb_decode(hb_handle* h, const uint8_t* bytes, const uint64_t* off, const ui
  * or tick produces (MsgAppResp, MsgHeartbeatResp, MsgVoteResp, MsgHeartbeat
  * and, in vote mode, campaign's MsgVote: no entries, the empty snapshot) leave
  * the device as the bytes
+ * (in append mode a leader's MsgApp too: all of it but the entry payloads, which
+ * the host splices in at a place the device names)
  * Message.MarshalTo writes (raft/raftpb/raft.pb.go:1271-1330), ready for the
  * transport, without the host replaying an event.  Two calls, both
  * asynchronous on the handle's stream:
@@ -549,13 +551,13 @@ int  hb_decode(hb_handle* h, const uint8_t* bytes, const uint64_t* off, const ui
  * A batch is a structure of arrays in device memory, capacity `cap` records: */
 typedef struct hb_out_batch {
   uint32_t* group;    /* group slot                                                   */
-  uint32_t* info;     /* HB_INFO(type, to_ref, reject) [| HB_OUT_HOST]; to_ref = slot or HB_REF_OTHER */
+  uint32_t* info;     /* HB_INFO(type, to_ref, reject) [| HB_OUT_HOST | HB_OUT_ENTS]; to_ref = slot or HB_REF_OTHER */
   uint64_t* to;       /* m.To as a node id (0 when to_ref == HB_REF_OTHER)            */
   uint64_t* term;     /* m.Term */
   uint64_t* log_term; /* m.LogTerm */
   uint64_t* index;    /* m.Index */
   uint64_t* commit;   /* m.Commit */
-  uint64_t* hint;     /* m.RejectHint */
+  uint64_t* hint;     /* m.RejectHint; with HB_OUT_ENTS the index of the last entry carried */
 } hb_out_batch;
 /* Egress on (any non-zero `on`): every later hb_step / hb_tick first copies the
  * groups' Term and lastIndex columns (16 B per group, allocated here) so that
@@ -570,19 +572,39 @@ typedef struct hb_out_batch {
  * hb_egress's output are what they were before the bit existed.  A call that
  * changes the mode while egress is on waits for the stream, allocates or frees
  * the column, and hb_egress gives count 0 until the next step or tick (the
- * step before the call has no matching snapshot). */
+ * step before the call has no matching snapshot).
+ * Bit HB_EGRESS_APPS adds append mode: the lastTerm column as in vote mode,
+ * the committed column and the boundary pair (the index just below the
+ * current-term run and its term; 32 B per group more than plain egress, and a
+ * group with a current-term run reads its term-run ring), and hb_egress also
+ * makes sendAppend's MsgApp records.  The bits combine: the modes are 0, 1, 3,
+ * 5 and 7.  Without the bit the kernels launched, the bytes the snapshot moves
+ * and every output are what they were before the bit existed; a change of this
+ * bit while egress is on behaves like a change of the vote bit. */
 #define HB_EGRESS_ON    1
 #define HB_EGRESS_VOTES 2
+#define HB_EGRESS_APPS  4
 int  hb_set_egress(hb_handle* h, int on);
-/* The mode in force: 0 (off), HB_EGRESS_ON, or HB_EGRESS_ON | HB_EGRESS_VOTES;
- * HB_EINVAL for a NULL handle.  Vote mode is an addition inside ABI 8 (every
+/* The mode in force: 0 (off), or HB_EGRESS_ON | any of HB_EGRESS_VOTES and
+ * HB_EGRESS_APPS (0, 1, 3, 5, 7); HB_EINVAL for a NULL handle.  Vote mode is an addition inside ABI 8 (every
  * value of `on` used before keeps its meaning), so the version number does not
  * tell whether a library knows the bit: one that lacks this function does not
  * (it takes any non-zero `on` as HB_EGRESS_ON and makes no vote record). */
 int  hb_egress_mode(hb_handle* h);
+/* The mode bits this library knows (HB_EGRESS_ON | HB_EGRESS_VOTES | HB_EGRESS_APPS): append
+ * mode is an addition inside ABI 8 too, and a library that lacks this function lacks it. */
+int  hb_egress_caps(void);
 /* A vote record whose LogTerm the device cannot tell: info carries this flag
- * and log_term = 0; the host builds the message from its event as before. */
+ * and log_term = 0; the host builds the message from its event as before.
+ * Likewise a MsgApp record of append mode whose LogTerm, Commit or entry range
+ * the device cannot tell: log_term = commit = hint = 0, only to, term and index
+ * are the message's. */
 #define HB_OUT_HOST     0x400u
+/* A MsgApp record that carries entries (index, hint]: the hint column holds the
+ * index of the last entry, not a RejectHint (a MsgApp's RejectHint is 0).  No
+ * other consumer of info gives bit 11 a meaning: hb_encode reads bits 0-3, 4-7,
+ * 8 and HB_OUT_HOST, hb_egress_bin bits 4-7. */
+#define HB_OUT_ENTS     0x800u
 /* One record per HB_EV_RESP / HB_EV_HEARTBEAT event of the last step or tick
  * (since hb_set_egress), in chunk order then word order of hb_events_device:
  * a group's records are in the order the reference appended the messages to
@@ -599,24 +621,54 @@ int  hb_egress_mode(hb_handle* h);
  * restored a snapshot earlier in the same call (the events carry no entry
  * terms), or when its last index lay below the current-term run and its term
  * runs were never loaded (hb_load_term_runs); a campaign from hb_tick never is.
- * Messages with entries or a snapshot (HB_EV_APP / _SNAP, HB_EV_PROP_FWD), and
- * without vote mode HB_EV_VOTE, make no record: the host builds them as
- * before.  self_id is this node's id; a record holds no sender (hb_encode
+ * Append mode: also one MsgApp record per HB_EV_APP event (one per slot of a
+ * broadcast word's mask, in slot order, at consecutive output positions):
+ * info = HB_INFO(HB_MSG_APP, slot, 0), m.Term = the Term at the send, m.Index =
+ * the event's x, m.Commit = raftLog.committed at the send (the pre-step column,
+ * then each HB_EV_COMMIT), m.LogTerm = the Term when the event's aux bit is set,
+ * else the term of the index just below the current-term run when x is that
+ * index (a new leader's first bcastAppend) and the device knows it.  With no
+ * entries to send (x >= lastIndex at the send) hint = 0 and the record is an
+ * ordinary payload-free one.  With entries info carries HB_OUT_ENTS and hint =
+ * L, the last entry's index: lastIndex at the send under max_msg_size
+ * HB_NO_LIMIT, x + 1 under max_msg_size 0.  The record is flagged HB_OUT_HOST
+ * instead (log_term = commit = hint = 0) when the device cannot prove a value:
+ * entries under a finite non-zero max_msg_size (limitSize's cut is in no
+ * event), an aux = 0 send anywhere but at a known boundary, or any send after
+ * the group appended a leader's entries or restored a snapshot earlier in the
+ * same call until an HB_EV_COMMIT (Commit) and an HB_EV_TERM with a known
+ * lastTerm (LogTerm) re-establish them.
+ * Messages with a snapshot (HB_EV_SNAP) and HB_EV_PROP_FWD, without append mode
+ * HB_EV_APP and without vote mode HB_EV_VOTE, make no record: the host builds
+ * them as before.  self_id is this node's id; a record holds no sender (hb_encode
  * writes m.From), so hb_egress only takes it for symmetry with hb_encode.
  * *count (device-readable: device memory or hb_alloc_pinned memory) = the
  * number of records; when it exceeds cap only the first cap are written (a cut
  * may fall between two records of one broadcast word) and the caller calls
- * again (the events stay valid until the next step). */
+ * again (the events stay valid until the next step).  hb_egress itself puts no
+ * bound on cap; hb_encode's and hb_egress_bin's (max_batch x (max_replicas + 4))
+ * holds a MsgApp to every peer for every stepped message, so it is wide enough
+ * for append mode whenever the step's dense proposals are no more than
+ * 4 max_batch / (max_replicas - 1): a 1M x 3 step of one proposal and two acks
+ * per group (max_batch >= 2M) makes 4M records against a bound of 14M. */
 int  hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t cap, uint64_t* count);
 /* Record i (m.From = self_id) becomes bytes[off[i], off[i+1]), packed densely
  * in record order, 28 to 91 bytes each; off[n] and *total = the byte count.
  * n = *n_dev (device-readable like *total, e.g. hb_egress's count, clamped to
  * cap; NULL = cap).  status[i] = HB_WIRE_OK, or HB_WIRE_HOST with length 0 for
  * a record whose to_ref is HB_REF_OTHER or whose info carries HB_OUT_HOST.
+ * A record with HB_OUT_ENTS (and without HB_OUT_HOST) is written as prefix ||
+ * suffix, the bytes of the same message without entries (fields 1-6, then
+ * fields 8-11: Commit, the empty snapshot, Reject = 0, RejectHint = 0; still
+ * 28 to 91 bytes), and status[i] = HB_WIRE_SPLICE | prefix_len (at most 57).
+ * The full message is bytes[off[i], off[i] + prefix_len), then for each entry
+ * of (index, hint] the bytes 0x3a, varint(Entry.Size()), Entry, then the rest of
+ * the record: a three-part gather write.
  * When *total > bytes_cap no byte is
  * written (off, status and total are): call again with a larger buffer, 91 x n
  * always suffices.  HB_EINVAL before any device work: a NULL handle or array,
  * cap > max_batch x (max_replicas + 4), cap x 91 >= 2^32. */
+#define HB_WIRE_SPLICE 0x80  /* hb_encode status bit: low 7 bits = where the entries go */
 int  hb_encode(hb_handle* h, const hb_out_batch* in, uint64_t cap, const uint64_t* n_dev, uint64_t self_id,
                uint8_t* bytes, uint64_t bytes_cap, uint64_t* off /* [cap + 1] */, uint8_t* status /* [cap] */,
                uint64_t* total);
@@ -645,7 +697,8 @@ int  hb_set_egress_peers(hb_handle* h, const uint64_t* ids, uint32_t n);
  * src[j] (optional, may be NULL) = the index in `in` of output record j.
  * Bin of a record: to_ref == HB_REF_OTHER -> "other"; else the b with ids[b] == to
  * (all 64 bits); no such b -> "other".
- * A record flagged HB_OUT_HOST moves like any other: binned by its `to`, info unchanged.
+ * A record flagged HB_OUT_HOST or HB_OUT_ENTS moves like any other: binned by its `to`,
+ * info and hint unchanged, so append mode needs nothing from hb_egress_bin or hb_peer_spans.
  * Records of `out` (and src) at and past n are not written; `in` is not written.
  * n = 0 and cap = 0 are legal: bin_off is then all zeros.
  * HB_EINVAL before any device work: NULL handle / batch / array / bin_off, no table set,

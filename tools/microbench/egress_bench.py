@@ -13,6 +13,12 @@ Workloads on a handle of 1,048,576 groups x 3:
           mode on (hb_set_egress bit HB_EGRESS_VOTES): two MsgVote per group,
           every group one EVC_VBCAST word.
 
+  cfg2    (--workload cfg2, a run of its own) the headline step of bench.py in
+          append mode (hb_set_egress bit HB_EGRESS_APPS, mode 5): one dense
+          proposal and two acks per group, so every group sends four MsgApp,
+          two with the new entry (spliced by the host) and two with only the
+          new Commit; every group's older term run is loaded, as a node's are.
+
 Per workload: the step (or tick) runs once with egress on, then hb_egress +
 hb_encode (chained through the device-resident count, no host sync between
 them) run 3 warm-up and 25 timed times over that step's events, each pair
@@ -21,7 +27,7 @@ in microseconds, the records and wire bytes, and the bytes of a model with the
 rate it implies at the median:
 
   events read (8 B per word) + the snapshot (16 B per group, 24 B in vote
-  mode: lterm0) + the peer id (8 B per record) + the record written and read
+  mode: lterm0, 48 B in append mode: lterm0, commit0, bl0, blt0) + the peer id (8 B per record) + the record written and read
   back (56 + 52 B) + the wire bytes written.
 
 (The model counts the event words once; hb_egress's count pass reads them a
@@ -31,6 +37,7 @@ back-to-back steps of the follow and the cfg2 workload with egress off, on
 
   python tools/microbench/egress_bench.py [--out profiles/egress_bench.json]
   python tools/microbench/egress_bench.py --workload campaign [--out profiles/egress_vote_bench.json]
+  python tools/microbench/egress_bench.py --workload cfg2 [--out profiles/egress_app_bench.json]
 """
 import argparse
 import json
@@ -117,16 +124,100 @@ def steps_ms(torch, stream, one, steps, warmup=5):
     return e0.elapsed_time(e1) / steps
 
 
+def load_one_older_run(eng, g):
+    """hb_load_term_runs for every group at once: the run below the current-term run of
+    synth.steady_groups logs, (0, Term - 1)."""
+    from etcd_amd import hipbatch
+    n = len(g)
+    gs, ns = np.arange(n, dtype=np.uint32), np.ones(n, dtype=np.uint32)
+    flat = np.zeros((n, 2), dtype=np.uint64)
+    flat[:, 1] = np.maximum(g["term"].astype(np.int64) - 1, 0).astype(np.uint64)
+    rc = hipbatch.lib().hb_load_term_runs(eng.h, n, gs.ctypes.data, ns.ctypes.data, flat.ctypes.data)
+    assert rc == abi.HB_OK, rc
+
+
+def snapshot_modes(torch, stream, eng, one, steps, name):
+    """ms per step of `one` with egress off, then mode 1, then mode 5 (K back-to-back steps each)."""
+    span = 5 + steps
+    off_ms = steps_ms(torch, stream, one, steps)
+    eng.set_egress(True)
+    on_ms = steps_ms(torch, stream, lambda k: one(span + k), steps)
+    eng.set_egress(True, apps=True)
+    apps_ms = steps_ms(torch, stream, lambda k: one(2 * span + k), steps)
+    return dict(workload=name, steps=steps, ms_per_step_egress_off=off_ms, ms_per_step_egress_on=on_ms,
+                ms_per_step_egress_apps=apps_ms)
+
+
+def cfg2_main(args, torch, stream):
+    results, snapshot = [], []
+    # ---- follow steps: egress off / mode 1 / mode 5 ------------------------------------------
+    seed = 0x5EED0006
+    g, _ = synth.follow_groups(G, N, seed=seed, with_runs=False)
+    b = synth.follow_batch(g, 0, seed=seed)
+    eng = Engine(G, max_replicas=N, max_inflight=W, max_batch=len(b["group"]), stream=stream)
+    eng.load_groups(g)
+    eng.load_peers(peers())
+    d = {k: dv(torch, b[k]) for k in ("group", "info", "term", "hint", "eoff", "eterm", "index", "commit")}
+    i_inc = dv(torch, ((b["info"] & 0xF) == abi.HB_MSG_APP).astype(np.uint64))
+
+    def follow(k):
+        eng.step(d["group"], d["info"], d["term"], d["index"] + i_inc * k, d["hint"], None, host=False,
+                 eoff=d["eoff"], commit=d["commit"] + k, eterm=d["eterm"])
+    snapshot.append(snapshot_modes(torch, stream, eng, follow, args.steps, "follow"))
+    eng.close()
+    del d
+    # ---- cfg2 steps: egress off / mode 1 / mode 5, then one step's hb_egress + hb_encode -------
+    seed = 0x5EED0002
+    g, _ = synth.steady_groups(G, N, seed=seed, with_runs=False)
+    eng = Engine(G, max_replicas=N, max_inflight=W, max_batch=2 * G, stream=stream)
+    eng.load_groups(g)
+    eng.load_peers(peers())
+    load_one_older_run(eng, g)
+    b0 = synth.cfg2_batch(g, 0, seed=seed)  # step k acks last + k + 1 (the same arrival order every step)
+    x = {k: dv(torch, b0[k]) for k in ("group", "info", "term", "index", "props")}
+
+    def cfg2(k):
+        eng.step(x["group"], x["info"], x["term"], x["index"] + k, None, x["props"], host=False)
+    snapshot.append(snapshot_modes(torch, stream, eng, cfg2, args.steps, "cfg2"))
+    print(json.dumps(snapshot), flush=True)
+    assert eng.egress_mode() == abi.HB_EGRESS_ON | abi.HB_EGRESS_APPS
+    cfg2(3 * (5 + args.steps))
+    sink = Sink(torch, 4 * G)
+    us = timed(torch, stream, eng, sink, args.reps)
+    r = report("cfg2: one proposal and two acks per group, four MsgApp each (append mode)", eng, sink, us, args.reps,
+               snap=48)
+    info = sink.out["info"].cpu().numpy().view(np.uint32)
+    status = sink.status.cpu().numpy()
+    r["records_spliced"] = int((status & abi.HB_WIRE_SPLICE != 0).sum())
+    r["records_flagged"] = int((info & abi.HB_OUT_HOST != 0).sum())
+    r["records_entries_flag"] = int((info & abi.HB_OUT_ENTS != 0).sum())
+    print(json.dumps({k: r[k] for k in ("records", "records_spliced", "records_flagged")}), flush=True)
+    assert r["records"] == 4 * G and ((info & 0xF) == abi.HB_MSG_APP).all()
+    assert r["records_spliced"] == r["records_entries_flag"] == 2 * G and r["records_flagged"] == 0
+    assert (status[info & abi.HB_OUT_ENTS == 0] == abi.HB_WIRE_OK).all()
+    results.append(r)
+    eng.close()
+    return dict(bench="hb_egress + hb_encode, append mode", results=results, snapshot_cost=snapshot)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--workload", choices=("egress", "campaign"), default="egress")
+    ap.add_argument("--workload", choices=("egress", "campaign", "cfg2"), default="egress")
     args = ap.parse_args()
     import torch
     stream = torch.cuda.Stream()
     results, snapshot = [], []
+    if args.workload == "cfg2":
+        with torch.cuda.stream(stream):
+            out = cfg2_main(args, torch, stream)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     with torch.cuda.stream(stream):
         # ---- follow ---------------------------------------------------------------------
         seed = 0x5EED0006
