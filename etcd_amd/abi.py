@@ -112,6 +112,7 @@ HB_WIRE_HOST = 2
 HB_WIRE_ERROR = 3
 HB_WIRE_PANIC = 4
 HB_WIRE_BADGROUP = 5
+HB_DECODE_FOLLOW = 1      # hb_decode_caps bit: hb_decode_follow
 
 HB_STAT_MSGS = 0
 HB_STAT_APPRESP = 1

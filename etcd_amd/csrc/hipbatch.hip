@@ -28,6 +28,7 @@
 #include "hipbatch_elect.h"
 #include "hipbatch_lead.h"
 #include "hipbatch_wire.h"
+#include "hipbatch_wire_in.h"
 #include "hipbatch_wire_out.h"
 #include "hipbatch_bin.h"
 
@@ -3059,6 +3060,297 @@ __global__ void __launch_bounds__(DEC_THREADS) k_decode_general(DecodeArgs a, co
   }
 }
 
+// ---------------------------------------------------------------------------
+// hb_decode_follow: hb_decode plus the follower side.  MsgApp
+// (with its entries), MsgHeartbeat and MsgVote become batch records too; the
+// entry run of record i goes to eterm / edesc / edata at eoff[i].
+//   k_decf_parse    a lane per record: the canonical-shape parser
+//                   (hipbatch_wire_in.h) from the wave's LDS window, or from
+//                   global memory when the wave's span does not fit (one long
+//                   payload is enough); batch record, status, the record's
+//                   entry count scanned inside the workgroup (eoff[i] = the
+//                   prefix in its workgroup, bsum = the workgroup's sum).  Any
+//                   other shape is queued.
+//   k_decf_general  Message.Unmarshal over the queue, as k_decode_general; a
+//                   queued record never has an entry run.
+//   k_decf_scan     one workgroup: the workgroups' bases, the total, eoff[n],
+//                   the sentinel record n.
+//   k_decf_write    a lane per record: eoff[i] += its workgroup's base, then the
+//                   lanes with entries walk their record again (global memory)
+//                   and write the run, unless the total exceeds ent_cap.
+//   k_decf_small    scan + write in one workgroup (the small-step rule).
+// ---------------------------------------------------------------------------
+struct DecfArgs {
+  DecodeArgs d;
+  uint64_t* o_commit;
+  uint64_t* eoff;
+  uint64_t* eterm;
+  uint32_t* edesc;
+  uint64_t* edata;
+  uint64_t ent_cap;
+  uint64_t* n_ent;
+  uint32_t* bsum;   // [workgroups of k_decf_parse] entries per workgroup
+  uint64_t* bbase;  // [workgroups + 1] their exclusive scan, then the total
+};
+constexpr uint32_t DECF_WIN = 8192;  // bytes staged per wave: 128 a record (a MsgApp with one small entry is ~70)
+constexpr uint32_t DECF_SMALL_MAX = 16384;  // the small-step rule: scan and write in one workgroup
+static_assert(WI_ENT_MAX_DATA == HB_ENT_MAX_DATA && (uint64_t)DEC_THREADS * WI_MAX_ENTS < (1ull << 32),
+              "descriptor layout; a workgroup's entry count fits 32 bits");
+static_assert(DECF_SMALL_MAX <= DEC_THREADS * DEC_THREADS, "k_decf_small scans one workgroup sum per lane");
+static_assert((DEC_THREADS / 64) * (DECF_WIN + 32) <= 40 * 1024, "four workgroups of k_decf_parse per CU (160 KiB LDS)");
+
+// Outcome of one record -> batch record + status (both passes).  nent: the
+// field-7 occurrences; canon: the record has the canonical shape and its
+// entries pass the checks.  Returns whether the record keeps an entry run.
+__device__ __forceinline__ bool decf_emit(const DecfArgs& a, uint64_t k, int rc, const WireMsgF& f, bool canon,
+                                          uint32_t g, bool gok, const uint64_t* ids) {
+  const WireMsg& m = f.m;
+  const bool resp = m.type == HB_MSG_APP_RESP || m.type == HB_MSG_VOTE_RESP || m.type == HB_MSG_HEARTBEAT_RESP;
+  const bool fol = m.type == HB_MSG_APP || m.type == HB_MSG_HEARTBEAT || m.type == HB_MSG_VOTE;
+  uint32_t slot = HB_SLOT_NONE;
+  if (rc == W_OK && (resp || fol) && gok && a.d.peer && m.from != 0) {
+    const uint32_t nn = (uint32_t)ids[HB_PEER_ROW - 1];
+#pragma unroll
+    for (uint32_t s = 0; s < HB_MAX_REPLICAS; ++s)
+      if (s < nn && slot == HB_SLOT_NONE && ids[s] == m.from) slot = s;
+  }
+  uint32_t st;
+  if (rc == W_ERR) st = HB_WIRE_ERROR;
+  else if (rc == W_PANIC) st = HB_WIRE_PANIC;
+  else if (rc == W_DEEP) st = HB_WIRE_HOST;
+  else if (m.type == HB_MSG_HUP || m.type == HB_MSG_BEAT || m.type == HB_MSG_UNREACHABLE ||
+           m.type == HB_MSG_SNAP_STATUS)
+    st = HB_WIRE_LOCAL;  // IsLocalMsg raft/util.go:49-51
+  else if (resp) st = gok ? HB_WIRE_OK : HB_WIRE_BADGROUP;
+  else if (!fol || !gok) st = HB_WIRE_HOST;  // (hb_decode's precedence: the type rule comes before the group's)
+  else if (m.type == HB_MSG_VOTE) st = slot != HB_SLOT_NONE ? HB_WIRE_OK : HB_WIRE_HOST;  // HB_INFO_VOTED: the host's
+  else if (m.type == HB_MSG_APP) st = (f.f.nentries == 0 || canon) ? HB_WIRE_OK : HB_WIRE_HOST;
+  else st = HB_WIRE_OK;  // MsgHeartbeat
+  const bool ok = st == HB_WIRE_OK;
+  uint64_t hint = m.hint, commit = 0;
+  if (fol) {
+    hint = m.type == HB_MSG_HEARTBEAT ? 0ull : f.f.log_term;
+    commit = m.type == HB_MSG_VOTE ? 0ull : f.f.commit;
+  }
+  a.d.o_group[k] = ok ? g : 0xFFFFFFFFu;
+  a.d.o_info[k] = ok ? ((uint32_t)m.type | (slot << 4) | ((uint32_t)m.reject << 8)) : 0u;
+  a.d.o_term[k] = ok ? m.term : 0ull;
+  a.d.o_index[k] = ok ? m.index : 0ull;
+  a.d.o_hint[k] = ok ? hint : 0ull;
+  a.o_commit[k] = ok ? commit : 0ull;
+  a.d.status[k] = (uint8_t)st;
+  return ok && m.type == HB_MSG_APP && f.f.nentries != 0;
+}
+
+__device__ __forceinline__ bool decf_canon(const uint8_t* p, uint32_t len, WireMsgF* f) {
+  WiHeader h;
+  WiTail t;
+  uint32_t ne = 0;
+  if (!wi_message(p, len, &h, &t, &ne)) return false;
+  f->m.type = (int32_t)h.type;
+  f->m.from = h.from;
+  f->m.term = h.term;
+  f->m.index = h.index;
+  f->m.hint = t.hint;
+  f->m.reject = t.reject;
+  f->f.log_term = h.log_term;
+  f->f.commit = t.commit;
+  f->f.nentries = ne;
+  return true;
+}
+
+__global__ void __launch_bounds__(DEC_THREADS) k_decf_parse(DecfArgs a, uint32_t* q, uint32_t* qn) {
+  __shared__ uint4 l_win[DEC_THREADS / 64][DECF_WIN / 16 + 2];
+  __shared__ uint32_t sh16[16];
+  const DecodeArgs& A_ = a.d;
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t k = (uint64_t)blockIdx.x * DEC_THREADS + threadIdx.x;
+  const bool live = k < A_.n;
+  const uint64_t o = live ? A_.off[k] : 0ull;
+  const uint32_t len = live ? A_.len[k] : 0u;
+  uint64_t lo = live ? o : ~0ull, hi = live ? o + len : 0ull;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const uint64_t l2 = __shfl_xor(lo, d), h2 = __shfl_xor(hi, d);
+    lo = l2 < lo ? l2 : lo;
+    hi = h2 > hi ? h2 : hi;
+  }
+  const bool fits = hi > lo && hi - lo <= DECF_WIN;  // uniform in the wave
+  uint8_t* win = reinterpret_cast<uint8_t*>(&l_win[wave][0]);
+  const uintptr_t A = reinterpret_cast<uintptr_t>(A_.bytes) + lo, B = reinterpret_cast<uintptr_t>(A_.bytes) + hi;
+  const uintptr_t base = A & ~(uintptr_t)15;
+  if (fits) {
+    const uintptr_t A16 = (A + 15) & ~(uintptr_t)15, B16 = B & ~(uintptr_t)15;
+    if (A16 < B16) {
+      const uint32_t nc = (uint32_t)((B16 - A16) >> 4), c0 = (uint32_t)((A16 - base) >> 4);
+      for (uint32_t c = lane; c < nc; c += 64) l_win[wave][c0 + c] = reinterpret_cast<const uint4*>(A16)[c];
+      for (uintptr_t x = A + lane; x < A16; x += 64) win[x - base] = *reinterpret_cast<const uint8_t*>(x);
+      for (uintptr_t x = B16 + lane; x < B; x += 64) win[x - base] = *reinterpret_cast<const uint8_t*>(x);
+    } else {
+      for (uintptr_t x = A + lane; x < B; x += 64) win[x - base] = *reinterpret_cast<const uint8_t*>(x);
+    }
+  }
+  __syncthreads();
+  // (no early exit: every lane takes part in the workgroup's scan below)
+  const uint32_t g = live ? A_.group[k] : 0u;
+  const bool gok = live && g < A_.G;
+  uint4 prow[4] = {};
+  if (gok && A_.peer) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) prow[j] = A_.peer[(size_t)g * 4 + j];
+  }
+  WireMsgF f;
+  bool canon = false;
+  if (live) {
+    // a wave whose span does not fit (a long payload among its records) parses from global memory:
+    // one copy of the parser behind a flat pointer, chosen per wave
+    const uint8_t* src = fits ? win + (reinterpret_cast<uintptr_t>(A_.bytes) + o - base) : A_.bytes + o;
+    canon = decf_canon(src, len, &f);
+  }
+  // wave-aggregated append of the other records to the general pass's queue
+  const bool slowl = live && !canon;
+  const uint64_t slow = __ballot(slowl);
+  if (slow) {
+    const uint32_t cnt = (uint32_t)__popcll(slow);
+    const uint32_t leader = (uint32_t)__ffsll((long long)slow) - 1;
+    uint32_t b0 = 0;
+    if (lane == leader) b0 = atomicAdd(qn, cnt);
+    b0 = __shfl(b0, (int)leader);
+    if (slowl) q[b0 + (uint32_t)__popcll(slow & ((1ull << lane) - 1))] = (uint32_t)k;
+  }
+  uint32_t ne = 0;
+  if (canon && decf_emit(a, k, W_OK, f, true, g, gok, reinterpret_cast<const uint64_t*>(prow))) ne = f.f.nentries;
+  uint32_t tot;
+  const uint32_t ex = block_excl_scan(ne, sh16, &tot);
+  if (live) a.eoff[k] = ex;
+  if (threadIdx.x == 0) a.bsum[blockIdx.x] = tot;
+}
+
+__global__ void __launch_bounds__(DEC_THREADS) k_decf_general(DecfArgs a, const uint32_t* q, uint32_t* qn) {
+  const uint32_t total = *(volatile uint32_t*)qn;
+  for (uint32_t j = blockIdx.x * DEC_THREADS + threadIdx.x; j < total; j += gridDim.x * DEC_THREADS) {
+    const uint64_t k = q[j];
+    const uint32_t g = a.d.group[k];
+    const bool gok = g < a.d.G;
+    uint64_t ids[HB_PEER_ROW] = {};
+    if (gok && a.d.peer) {
+      const uint64_t* row = reinterpret_cast<const uint64_t*>(a.d.peer) + (size_t)g * HB_PEER_ROW;
+#pragma unroll
+      for (uint32_t s = 0; s < HB_PEER_ROW; ++s) ids[s] = row[s];
+    }
+    WireMsgF f;
+    const int rc = w_unmarshal_follow(a.d.bytes + a.d.off[k], (int64_t)a.d.len[k], &f);
+    (void)decf_emit(a, k, rc, f, false, g, gok, ids);
+  }
+  // qn[1] counts finished workgroups; the last one resets both words
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence();
+    if (atomicAdd(qn + 1, 1u) == gridDim.x - 1) {
+      qn[0] = 0;
+      qn[1] = 0;
+      __threadfence();
+    }
+  }
+}
+
+// Block-wide exclusive scan of 64-bit values (any blockDim.x that is a multiple of 64).
+__device__ __forceinline__ uint64_t block_excl_scan64(uint64_t v, uint64_t* sh16, uint64_t* total) {
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  uint64_t incl = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint64_t t = __shfl_up(incl, d);
+    if (lane >= (uint32_t)d) incl += t;
+  }
+  if (lane == 63) sh16[wave] = incl;
+  __syncthreads();
+  uint64_t before = 0, tot = 0;
+  for (uint32_t w = 0; w < nw; ++w) {
+    const uint64_t x = sh16[w];
+    if (w < wave) before += x;
+    tot += x;
+  }
+  *total = tot;
+  __syncthreads();
+  return before + incl - v;
+}
+
+// The total, eoff[n] and record n: a dropped record, so that a step over n + 1
+// records with n_edesc = ent_cap reads the count nowhere (include/hipbatch.h).
+__device__ __forceinline__ void decf_finish(const DecfArgs& a, uint64_t tot) {
+  const uint64_t n = a.d.n;
+  a.eoff[n] = tot;
+  *a.n_ent = tot;
+  a.d.o_group[n] = 0xFFFFFFFFu;
+  a.d.o_info[n] = 0u;
+  a.d.o_term[n] = 0ull;
+  a.d.o_index[n] = 0ull;
+  a.d.o_hint[n] = 0ull;
+  a.o_commit[n] = 0ull;
+}
+
+// Workgroup `blk` of k_decf_parse, whose first entry is `base`: the final eoff,
+// and the entry runs when `write` (uniform).  eoff is rewritten in place: every
+// lane reads its own and its neighbour's local prefix before any lane writes.
+__device__ __forceinline__ void decf_write_block(const DecfArgs& a, uint64_t blk, uint64_t base, bool write) {
+  const uint64_t n = a.d.n, k = blk * DEC_THREADS + threadIdx.x;
+  const bool live = k < n;
+  uint64_t loc = 0, nxt = 0;
+  if (live) {
+    loc = a.eoff[k];
+    nxt = (threadIdx.x == DEC_THREADS - 1 || k + 1 == n) ? (uint64_t)a.bsum[blk] : a.eoff[k + 1];
+  }
+  __syncthreads();
+  if (!live) return;
+  const uint64_t e0 = base + loc, ne = nxt - loc;
+  a.eoff[k] = e0;
+  if (!write || ne == 0) return;
+  const uint64_t o = a.d.off[k];
+  const uint8_t* p = a.d.bytes + o;
+  const uint64_t l = a.d.len[k];
+  WiHeader h;
+  if (!wi_header(p, l, &h)) return;  // (pass one accepted it)
+  uint64_t i = h.ents;
+  for (uint64_t j = 0; j < ne; ++j) {
+    WiEntry e;
+    if (!wi_entry(p, l, i, h.index + 1 + j, &e)) return;
+    a.eterm[e0 + j] = e.term;
+    a.edesc[e0 + j] = e.desc;
+    a.edata[e0 + j] = e.data ? o + e.data : 0ull;
+  }
+}
+
+__global__ void __launch_bounds__(1024) k_decf_scan(DecfArgs a, uint32_t nblk) {
+  __shared__ uint64_t sh16[16];
+  const uint32_t per = (nblk + 1023) / 1024, b0 = threadIdx.x * per;
+  uint64_t sum = 0;
+  for (uint32_t i = b0; i < b0 + per && i < nblk; ++i) sum += a.bsum[i];
+  uint64_t tot;
+  uint64_t run = block_excl_scan64(sum, sh16, &tot);
+  for (uint32_t i = b0; i < b0 + per && i < nblk; ++i) {
+    a.bbase[i] = run;
+    run += a.bsum[i];
+  }
+  if (threadIdx.x == 0) {
+    a.bbase[nblk] = tot;
+    decf_finish(a, tot);
+  }
+}
+__global__ void __launch_bounds__(DEC_THREADS) k_decf_write(DecfArgs a, uint32_t nblk) {
+  decf_write_block(a, blockIdx.x, a.bbase[blockIdx.x], a.bbase[nblk] <= a.ent_cap);
+}
+// At most DECF_SMALL_MAX records (at most DEC_THREADS workgroups of k_decf_parse): scan and write.
+__global__ void __launch_bounds__(DEC_THREADS) k_decf_small(DecfArgs a, uint32_t nblk) {
+  __shared__ uint64_t sh16[16];
+  __shared__ uint64_t l_base[DEC_THREADS];
+  uint64_t tot;
+  l_base[threadIdx.x] = block_excl_scan64(threadIdx.x < nblk ? (uint64_t)a.bsum[threadIdx.x] : 0ull, sh16, &tot);
+  __syncthreads();
+  if (threadIdx.x == 0) decf_finish(a, tot);
+  for (uint32_t b = 0; b < nblk; ++b) decf_write_block(a, b, l_base[b], tot <= a.ent_cap);
+}
+
 // ============================================================================
 // Phase 3: finish
 // ============================================================================
@@ -4633,6 +4925,9 @@ struct hb_handle {
   uint32_t* dec_q = nullptr;      // hb_decode pass-2 queue (record indices)
   uint64_t dec_cap = 0;
   uint32_t* dec_qn = nullptr;     // [queue length, finished pass-2 workgroups]
+  uint32_t* decf_sum = nullptr;   // hb_decode_follow: [workgroups] entries per k_decf_parse workgroup, grown on demand
+  uint64_t* decf_base = nullptr;  // [workgroups + 1] their scan
+  uint64_t decf_cap = 0;          // workgroups the two hold
   void* evx = nullptr;            // hb_copy_events expansion scratch, grown on demand
   uint64_t evx_cap = 0;
   uint64_t* evw = nullptr;        // hb_events_to_host: per-chunk word offsets + total
@@ -5133,6 +5428,8 @@ int hb_destroy(hb_handle* h) {
   if (h->peer) (void)hipFree(h->peer);
   if (h->dec_q) (void)hipFree(h->dec_q);
   if (h->dec_qn) (void)hipFree(h->dec_qn);
+  if (h->decf_sum) (void)hipFree(h->decf_sum);
+  if (h->decf_base) (void)hipFree(h->decf_base);
   for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->lterm0, (void*)h->eg_commit0, (void*)h->bl0, (void*)h->blt0,
                   (void*)h->eg_cnt, (void*)h->eg_base, (void*)h->enc_sum,
                   (void*)h->enc_base, (void*)h->bin_table, (void*)h->bin_key, (void*)h->bin_hist})
@@ -5587,6 +5884,87 @@ int hb_decode(hb_handle* h, const uint8_t* bytes, const uint64_t* off, const uin
   const uint64_t gb = (n + DEC_THREADS - 1) / DEC_THREADS;
   hipLaunchKernelGGL(k_decode_general, dim3((unsigned)(gb < DEC_GEN_BLOCKS ? gb : DEC_GEN_BLOCKS)), dim3(DEC_THREADS), 0,
                      ds, da, h->dec_q, h->dec_qn);
+  HB_CHECK(hipGetLastError());
+  return HB_OK;
+}
+
+int hb_decode_caps(void) { return HB_DECODE_FOLLOW; }
+
+int hb_decode_follow(hb_handle* h, const uint8_t* bytes, const uint64_t* off, const uint32_t* len, const uint32_t* group,
+                     uint64_t n, const hb_batch* out, uint8_t* status, uint64_t ent_cap, uint64_t* edata,
+                     uint64_t* n_ent) {
+  if (!h || !out || !n_ent) return HB_EINVAL;
+  if (n >= (1ull << 32) || n + 1 > h->max_batch) return HB_EINVAL;  // record n is the sentinel
+  if (!out->group || !out->info || !out->term || !out->index || !out->hint || !out->commit || !out->eoff)
+    return HB_EINVAL;
+  if (n && (!bytes || !off || !len || !group || !status)) return HB_EINVAL;
+  if (ent_cap && (!out->eterm || !out->edesc || !edata)) return HB_EINVAL;
+  DeviceGuard guard(h->device);
+  DecfArgs fa;
+  DecodeArgs& da = fa.d;
+  da.bytes = bytes;
+  da.off = off;
+  da.len = len;
+  da.group = group;
+  da.n = n;
+  da.meta = h->st.meta;
+  da.peer = reinterpret_cast<const uint4*>(h->peer);
+  da.G = h->G;
+  da.nmax = h->nmax;
+  da.o_group = const_cast<uint32_t*>(out->group);
+  da.o_info = const_cast<uint32_t*>(out->info);
+  da.o_term = const_cast<uint64_t*>(out->term);
+  da.o_index = const_cast<uint64_t*>(out->index);
+  da.o_hint = const_cast<uint64_t*>(out->hint);
+  da.status = status;
+  fa.o_commit = const_cast<uint64_t*>(out->commit);
+  fa.eoff = const_cast<uint64_t*>(out->eoff);
+  fa.eterm = const_cast<uint64_t*>(out->eterm);
+  fa.edesc = const_cast<uint32_t*>(out->edesc);
+  fa.edata = edata;
+  fa.ent_cap = ent_cap;
+  fa.n_ent = dev_view(n_ent);
+  // on the stream the batches come from, as hb_decode
+  hipStream_t ds = h->in_stream_set ? h->in_stream : h->stream;
+  const uint64_t nblk = (n + DEC_THREADS - 1) / DEC_THREADS;
+  if (n > h->dec_cap) {  // the general pass's queue holds up to n record indices (shared with hb_decode)
+    HB_CHECK(hipStreamSynchronize(ds));
+    if (h->dec_q) (void)hipFree(h->dec_q);
+    h->dec_q = nullptr;
+    h->dec_cap = 0;
+    HB_CHECK(hipMalloc(&h->dec_q, n * sizeof(uint32_t)));
+    h->dec_cap = n;
+  }
+  if (!h->dec_qn) {
+    HB_CHECK(hipMalloc(&h->dec_qn, 2 * sizeof(uint32_t)));
+    HB_CHECK(hipMemsetAsync(h->dec_qn, 0, 2 * sizeof(uint32_t), ds));
+  }
+  if (nblk + 1 > h->decf_cap) {
+    HB_CHECK(hipStreamSynchronize(ds));
+    if (h->decf_sum) (void)hipFree(h->decf_sum);
+    if (h->decf_base) (void)hipFree(h->decf_base);
+    h->decf_sum = nullptr;
+    h->decf_base = nullptr;
+    h->decf_cap = 0;
+    HB_CHECK(hipMalloc(&h->decf_sum, (nblk + 1) * sizeof(uint32_t)));
+    HB_CHECK(hipMalloc(&h->decf_base, (nblk + 2) * sizeof(uint64_t)));
+    h->decf_cap = nblk + 1;
+  }
+  fa.bsum = h->decf_sum;
+  fa.bbase = h->decf_base;
+  if (nblk) {
+    hipLaunchKernelGGL(k_decf_parse, dim3((unsigned)nblk), dim3(DEC_THREADS), 0, ds, fa, h->dec_q, h->dec_qn);
+    HB_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_decf_general, dim3((unsigned)(nblk < DEC_GEN_BLOCKS ? nblk : DEC_GEN_BLOCKS)), dim3(DEC_THREADS),
+                       0, ds, fa, h->dec_q, h->dec_qn);
+    HB_CHECK(hipGetLastError());
+  }
+  if (n <= DECF_SMALL_MAX && !h->no_small) {
+    hipLaunchKernelGGL(k_decf_small, dim3(1), dim3(DEC_THREADS), 0, ds, fa, (uint32_t)nblk);
+  } else {
+    hipLaunchKernelGGL(k_decf_scan, dim3(1), dim3(1024), 0, ds, fa, (uint32_t)nblk);
+    if (nblk) hipLaunchKernelGGL(k_decf_write, dim3((unsigned)nblk), dim3(DEC_THREADS), 0, ds, fa, (uint32_t)nblk);
+  }
   HB_CHECK(hipGetLastError());
   return HB_OK;
 }

@@ -260,11 +260,29 @@ __device__ __forceinline__ bool w_fast_message(const uint8_t* d, int64_t l, Wire
   return true;
 }
 
-// Message.Unmarshal (raft/raftpb/raft.pb.go:549-799)
-__device__ int w_unmarshal_message(const uint8_t* d, int64_t l, WireMsg* m) {
+// What the follower side needs beyond WireMsg (hb_decode_follow).  LogTerm and Commit
+// OR-accumulate like the other varints; nentries counts the field-7 occurrences (what
+// len(m.Entries) becomes), whatever their contents.
+struct WireFollow {
+  uint64_t log_term, commit;
+  uint32_t nentries;
+};
+struct WireMsgF {
+  WireMsg m;
+  WireFollow f;
+};
+
+// Message.Unmarshal (raft/raftpb/raft.pb.go:549-799).  One body for both decoders: F = false
+// is hb_decode's (to, logTerm, commit decoded and dropped), F = true keeps them in *f too.
+template <bool F>
+__device__ __forceinline__ int w_unmarshal_t(const uint8_t* d, int64_t l, WireMsg* m, WireFollow* f) {
   m->type = 0;
   m->from = m->term = m->index = m->hint = 0;
   m->reject = false;
+  if constexpr (F) {
+    f->log_term = f->commit = 0;
+    f->nentries = 0;
+  }
   int64_t i = 0;
   for (int64_t it = 0; i < l; ++it) {
     if (it > l) return W_PANIC;  // a position repeats: Go never returns
@@ -283,6 +301,9 @@ __device__ int w_unmarshal_message(const uint8_t* d, int64_t l, WireMsg* m) {
       int64_t post;
       int rc = w_span(d, l, &i, &post);
       if (rc) return rc;
+      if constexpr (F) {
+        if (field == 7) ++f->nentries;
+      }
       rc = field == 7 ? w_parse_sub<0>(d + i, post - i) : w_parse_sub<2>(d + i, post - i);
       if (field == 7) {
         if (rc == W_PANIC || rc == W_DEEP) return rc;  // an Entry's error is dropped (:678)
@@ -310,9 +331,19 @@ __device__ int w_unmarshal_message(const uint8_t* d, int64_t l, WireMsg* m) {
     else if (field == 6) m->index |= v;
     else if (field == 10) m->reject = v != 0;  // assigned
     else if (field == 11) m->hint |= v;
-    // to (2), logTerm (5), commit (8): decoded, not needed by the batch
+    if constexpr (F) {
+      if (field == 5) f->log_term |= v;
+      else if (field == 8) f->commit |= v;
+    }
+    // to (2), and without F logTerm (5), commit (8): decoded, not needed by the batch
   }
   return W_OK;
+}
+__device__ int w_unmarshal_message(const uint8_t* d, int64_t l, WireMsg* m) {
+  return w_unmarshal_t<false>(d, l, m, nullptr);
+}
+__device__ int w_unmarshal_follow(const uint8_t* d, int64_t l, WireMsgF* x) {
+  return w_unmarshal_t<true>(d, l, &x->m, &x->f);
 }
 
 }  // namespace hb

@@ -121,6 +121,9 @@ def lib():
         "hb_load_peers": (C.c_int, [H, C.c_uint32, C.c_uint32, C.c_void_p]),
         "hb_decode": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, P(abi.hb_batch),
                                 C.c_void_p]),
+        "hb_decode_caps": (C.c_int, []),
+        "hb_decode_follow": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, P(abi.hb_batch),
+                                       C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
         "hb_set_egress": (C.c_int, [H, C.c_int]),
         "hb_egress_mode": (C.c_int, [H]),
         "hb_egress_caps": (C.c_int, []),
@@ -356,6 +359,31 @@ class Engine:
         self._keep_dec = (data, off, length, group, out, status)
         _check("hb_decode", lib().hb_decode(self.h, _ptr(data), _ptr(off), _ptr(length), _ptr(group), len(off),
                                             C.byref(b), _ptr(status)))
+
+    def decode_follow(self, data, off, length, group, out, status, ent_cap, edata, n_ent):
+        """hb_decode_follow: decode() plus the follower side (MsgApp with its entries, MsgHeartbeat,
+        MsgVote).  out = {group, info, term, index, hint, commit, eoff} of len(off) + 1 elements
+        (record n is the sentinel, eoff[n] the entry count) and {eterm, edesc} of ent_cap
+        entries; edata = device u64 [ent_cap] (where each entry's Data lies in `data`);
+        n_ent = a device (or pinned) u64 that takes the entry count.  When it exceeds ent_cap
+        no entry word is written.  Step the result with step_decoded()."""
+        b = abi.hb_batch()
+        b.n = len(off)
+        b.group, b.info, b.term, b.index = _ptr(out["group"]), _ptr(out["info"]), _ptr(out["term"]), _ptr(out["index"])
+        b.hint, b.props, b.commit = _ptr(out["hint"]), None, _ptr(out["commit"])
+        b.eoff, b.eterm, b.edesc = _ptr(out["eoff"]), _ptr(out.get("eterm")), _ptr(out.get("edesc"))
+        b.n_edesc = ent_cap
+        self._keep_decf = (data, off, length, group, out, status, edata, n_ent)
+        _check("hb_decode_follow", lib().hb_decode_follow(self.h, _ptr(data), _ptr(off), _ptr(length), _ptr(group),
+                                                          len(off), C.byref(b), _ptr(status), ent_cap, _ptr(edata),
+                                                          _ptr(n_ent)))
+
+    def step_decoded(self, out, ent_cap, props=None):
+        """Step what decode_follow() wrote, sentinel included (b.n = n + 1, n_edesc = ent_cap):
+        no host read of the entry count lies between the two calls."""
+        self.step(out["group"], out["info"], out["term"], out["index"], out["hint"], props, host=False,
+                  edesc=out.get("edesc") if ent_cap else None, eoff=out["eoff"], commit=out["commit"],
+                  eterm=out.get("eterm") if ent_cap else None)
 
     # ---- wire egress ---------------------------------------------------------------
     def set_egress(self, on=True, votes=False, apps=False):

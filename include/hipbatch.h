@@ -536,6 +536,57 @@ int  hb_load_peers(hb_handle* h, uint32_t first, uint32_t count, const uint64_t*
 int  hb_decode(hb_handle* h, const uint8_t* bytes, const uint64_t* off, const uint32_t* len,
                const uint32_t* group, uint64_t n, const hb_batch* out, uint8_t* status);
 
+/* hb_decode plus the follower side: the bytes one engine's hb_encode (and the
+ * host's splice of the entry payloads) writes, another engine steps.  Same
+ * inputs; status[i] is hb_decode's, except that these HB_WIRE_HOST records
+ * become HB_WIRE_OK batch records (the group being < capacity):
+ *   MsgHeartbeat             always: term, index, commit = m.Commit, hint = 0
+ *   MsgVote                  when m.From is a member of the group (a slot is
+ *                            found; HB_INFO_VOTED needs the host otherwise):
+ *                            term, index, hint = m.LogTerm
+ *   MsgApp without entries   always: term, index, hint = m.LogTerm, commit
+ *   MsgApp with entries      when the record has the shape Message.MarshalTo
+ *                            writes (fields 1-6 once and in order, the field-7
+ *                            run, field 8, the empty snapshot, fields 10 and
+ *                            11, the end; varints of at most 10 bytes) and
+ *                            every entry is 08 Type 10 Term 18 Index [22 len
+ *                            Data] ending at its span, with Type the one byte
+ *                            00 or 01, Index == m.Index + 1 + k and len(Data)
+ *                            <= HB_ENT_MAX_DATA: as above, plus its entry run
+ * Any other record Unmarshal accepts stays HB_WIRE_HOST (MsgSnap, MsgProp, a
+ * MsgApp whose entries have another shape or whose Entry error the reference
+ * drops).  The three response types give hb_decode's record with commit = 0.
+ * info = type | slot << 4 | reject << 8; a MsgApp or MsgHeartbeat from a
+ * non-member has slot HB_SLOT_NONE.
+ *
+ * Entries: out->eoff[i], i in [0, n], is the first entry of record i and
+ * eoff[n] = *n_ent the total (only HB_WIRE_OK MsgApp records have a run).  For
+ * entry k: out->eterm[k], out->edesc[k] = HB_ENT_DESC(len(Data), Type, field 4
+ * present), edata[k] = the offset in `bytes` of its first Data byte (0 when
+ * Data is absent): the host keeps its payloads from there.  eterm / edesc /
+ * edata hold ent_cap entries; when *n_ent > ent_cap none of their words is
+ * written (eoff, status, the batch and *n_ent are) and the caller calls again.
+ * The total of len[] / 8 always suffices: an entry is at least 8 wire bytes.
+ *
+ * The sentinel: the batch arrays of `out` (group, info, term, index, hint,
+ * commit) and eoff have n + 1 elements, and record n is written as a dropped
+ * record (group = 0xFFFFFFFF, the rest 0).  hb_step reads n_edesc only as the
+ * end of the LAST record's run, and only when that record is a valid MsgApp;
+ * so a caller steps b.n = n + 1 with b.n_edesc = ent_cap straight from these
+ * arrays, and decode -> step needs no host read of the count (it must still
+ * be <= ent_cap for the run to have been written).
+ *
+ * All arrays are device memory (bytes / off / len / group / status may be NULL
+ * when n = 0, eterm / edesc / edata when ent_cap = 0); n_ent is device or
+ * hb_alloc_pinned memory.  Asynchronous, on the stream hb_decode uses.
+ * HB_EINVAL before any device work: a NULL handle or array, n + 1 >
+ * max_batch, n >= 2^32.  n = 0 writes the sentinel, eoff[0] = 0, *n_ent = 0. */
+#define HB_DECODE_FOLLOW 1
+int  hb_decode_caps(void);   /* the decode features this library knows: HB_DECODE_FOLLOW */
+int  hb_decode_follow(hb_handle* h, const uint8_t* bytes, const uint64_t* off, const uint32_t* len,
+                      const uint32_t* group, uint64_t n, const hb_batch* out, uint8_t* status,
+                      uint64_t ent_cap, uint64_t* edata, uint64_t* n_ent);
+
 /* ---- wire egress ---------------------------------------------------------
  * The send path's counterpart of hb_decode: the payload-free messages a step
  * or tick produces (MsgAppResp, MsgHeartbeatResp, MsgVoteResp, MsgHeartbeat
