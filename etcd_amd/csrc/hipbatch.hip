@@ -21,8 +21,10 @@
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
+#include "hbmem.h"
 #include "hipbatch_kernels.h"
 #include "hipbatch_fast.h"
 #include "hipbatch_elect.h"
@@ -4772,6 +4774,42 @@ __global__ void __launch_bounds__(BIN_SLOTS + 64) k_peer_spans(const uint64_t* o
 // ============================================================================
 // host side
 // ============================================================================
+// Scratch that is allocated lazily or grown on demand is a DevBuf (hbmem.h):
+// it frees itself with its owner, and a failed allocation is HB_ENOMEM.
+struct HipDevice {
+  static void* alloc(size_t bytes) {
+    void* p = nullptr;
+    return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr;
+  }
+  static void free(void* p) { (void)hipFree(p); }
+};
+struct HipPinned {
+  static void* alloc(size_t bytes) {
+    void* p = nullptr;
+    return hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess ? p : nullptr;
+  }
+  static void free(void* p) { (void)hipHostFree(p); }
+};
+template <class T>
+using Dev = hbmem::DevBuf<T, HipDevice>;
+template <class T>
+using Pinned = hbmem::DevBuf<T, HipPinned>;
+// reserve() hook: the old block's last reader is a kernel or a copy on `s`
+inline auto stream_idle(hipStream_t s) {
+  return [s]() -> int {
+    HB_CHECK(hipStreamSynchronize(s));
+    return HB_OK;
+  };
+}
+// two buffers that exist together: both reserved, or both empty
+template <class A, class B>
+int reserve_pair(A& a, uint64_t na, B& b, uint64_t nb) {
+  if (a.reserve(na) == HB_OK && b.reserve(nb) == HB_OK) return HB_OK;
+  a.release();
+  b.release();
+  return HB_ENOMEM;
+}
+
 // What one step's prep (partition + route) hands to its apply.  Two sets, so
 // the prep of batch k+1 (on the prep stream) can run while batch k applies.
 struct PrepSet {
@@ -4782,8 +4820,7 @@ struct PrepSet {
   uint32_t* bk_fill = nullptr;    // [NBK] event words reserved in each bucket's region (k_route)
   uint32_t* ctr = nullptr;        // [CTR_WORDS] work-list counters + finish ticket (cleared by this set's prep)
   uint8_t* cnt = nullptr;         // [G]
-  uint8_t* dstage = nullptr;      // device copy of the packed host batch (grown on demand)
-  uint64_t dstage_cap = 0;
+  Dev<uint8_t> dstage;            // device copy of the packed host batch
   uint4* slot = nullptr;          // [route_kmax][G]
   uint64_t* side = nullptr;       // [2 max_batch] long records' (term, index)
   uint4* recx = nullptr;          // X mode: [max_batch] beside rec
@@ -4857,8 +4894,7 @@ struct hb_handle {
   // the log index (host mirror of DevState szx / trx: extent address | log2 capacity)
   LogPool pool;
   std::vector<uint64_t> h_szx, h_trx;
-  uint64_t* lx_jobs = nullptr;     // device scratch of hb_reserve_log's regrow jobs
-  uint64_t lx_jobs_cap = 0;
+  Dev<uint64_t> lx_jobs;          // hb_reserve_log's regrow jobs
   // partition scratch
   uint32_t* hist = nullptr;       // [tiles][RDX_BINS]
   uint32_t* n_valid = nullptr;    // messages kept after pass 1 (device)
@@ -4895,20 +4931,17 @@ struct hb_handle {
   uint64_t* s_eoff = nullptr;     // [max_batch]
   uint64_t* s_commit = nullptr;   // [max_batch]
   uint64_t* s_peoff = nullptr;    // [G] (finite max_msg_size)
-  uint32_t* s_edesc = nullptr;    // grown on demand
-  uint64_t s_edesc_cap = 0;
-  uint64_t* s_eterm = nullptr;    // grown on demand
-  uint64_t s_eterm_cap = 0;
+  Dev<uint32_t> s_edesc;          // [n_edesc]
+  Dev<uint64_t> s_eterm;          // [n_edesc]
   // events
   uint64_t* ev = nullptr;   // compact event words
   uint64_t ev_region = 0;  // records
   uint32_t ev_per_msg = 0;
   uint64_t* stats_shard = nullptr;  // shard_at(value, shard)
   uint64_t* stats_accum = nullptr;  // optional caller buffer (hb_set_stats_accum)
-  uint64_t* stats_pin = nullptr;    // [HB_STAT_COUNT] pinned readback (hb_copy_events' count)
+  Pinned<uint64_t> stats_pin;       // [HB_STAT_COUNT] readback (hb_copy_events' count)
   // host-pointer batches up to STAGE_MAX bytes: packed into one pinned block, one H2D copy
-  uint8_t* hstage = nullptr;        // pinned host block
-  uint64_t hstage_cap = 0;
+  Pinned<uint8_t> hstage;
   hipEvent_t hstage_done = nullptr; // the last copy out of hstage has completed
   uint64_t* stats = nullptr;
   // fast -> general hand-over
@@ -4921,49 +4954,40 @@ struct hb_handle {
   uint32_t* done = nullptr;       // k_apply workgroups finished this step
   uint32_t* resume = nullptr;     // [G]
   uint64_t* commit0 = nullptr;    // [G]
-  uint64_t* peer = nullptr;       // [G][HB_PEER_ROW] node ids (hb_load_peers), allocated on first use
-  uint32_t* dec_q = nullptr;      // hb_decode pass-2 queue (record indices)
-  uint64_t dec_cap = 0;
-  uint32_t* dec_qn = nullptr;     // [queue length, finished pass-2 workgroups]
-  uint32_t* decf_sum = nullptr;   // hb_decode_follow: [workgroups] entries per k_decf_parse workgroup, grown on demand
-  uint64_t* decf_base = nullptr;  // [workgroups + 1] their scan
-  uint64_t decf_cap = 0;          // workgroups the two hold
-  void* evx = nullptr;            // hb_copy_events expansion scratch, grown on demand
-  uint64_t evx_cap = 0;
-  uint64_t* evw = nullptr;        // hb_events_to_host: per-chunk word offsets + total
-  uint64_t evw_cap = 0;
+  Dev<uint64_t> peer;             // [G][HB_PEER_ROW] node ids (hb_load_peers)
+  Dev<uint32_t> dec_q;            // hb_decode pass-2 queue (record indices)
+  Dev<uint32_t> dec_qn;           // [queue length, finished pass-2 workgroups]
+  Dev<uint32_t> decf_sum;         // hb_decode_follow: [workgroups] entries per k_decf_parse workgroup
+  Dev<uint64_t> decf_base;        // [workgroups + 1] their scan (grown with decf_sum)
+  Dev<uint8_t> evx;               // hb_copy_events expansion scratch (bytes)
+  Dev<uint64_t> evw;              // hb_events_to_host: per-chunk word offsets + total
   // wire egress (hb_set_egress / hb_egress / hb_encode): nothing of it exists while egress is off
   bool egress = false;
   bool eg_stepped = false;        // a step or tick has run since hb_set_egress(on)
   bool eg_votes = false;          // HB_EGRESS_VOTES: MsgVote records, the lterm0 column
-  uint64_t* lterm0 = nullptr;     // [G] raftLog.lastTerm() before the last step / tick, or HB_LT_UNKNOWN
+  Dev<uint64_t> lterm0;           // [G] raftLog.lastTerm() before the last step / tick, or HB_LT_UNKNOWN
   bool eg_apps = false;           // HB_EGRESS_APPS: MsgApp records; lterm0 and the three columns below
-  uint64_t* eg_commit0 = nullptr; // [G] raftLog.committed before it (commit0 below is the step's own)
-  uint64_t* bl0 = nullptr;        // [G] the index just below the current-term run before it
-  uint64_t* blt0 = nullptr;       // [G] that index's term, or HB_LT_UNKNOWN
-  uint64_t* term0 = nullptr;      // [G] the term column before the last step / tick
-  uint64_t* last0 = nullptr;      // [G] the last column before it
-  uint32_t* eg_cnt = nullptr;     // [2 NB] records per chunk
-  uint64_t* eg_base = nullptr;    // [2 NB + 1] their scan
+  Dev<uint64_t> eg_commit0;       // [G] raftLog.committed before it (commit0 above is the step's own)
+  Dev<uint64_t> bl0;              // [G] the index just below the current-term run before it
+  Dev<uint64_t> blt0;             // [G] that index's term, or HB_LT_UNKNOWN
+  Dev<uint64_t> term0;            // [G] the term column before the last step / tick
+  Dev<uint64_t> last0;            // [G] the last column before it
+  Dev<uint32_t> eg_cnt;           // [2 NB] records per chunk
+  Dev<uint64_t> eg_base;          // [2 NB + 1] their scan
   // per-peer egress (hb_set_egress_peers / hb_egress_bin): nothing of it exists before the first table
-  BinTable* bin_table = nullptr;  // device copy of the node table
+  Dev<BinTable> bin_table;        // device copy of the node table
   uint32_t bin_np = 0;            // its ids (the table is set while bin_table is)
-  uint8_t* bin_key = nullptr;     // [largest batch] key bytes of the tiled path (allocated on first use)
-  uint32_t* bin_hist = nullptr;   // [256] bin totals, then [256][its tiles] tile histograms
-  uint32_t* enc_sum = nullptr;    // hb_encode: [blocks] bytes per pass-one workgroup (allocated on first use)
-  uint64_t* enc_base = nullptr;   // [blocks + 1]
-  uint64_t* rnd = nullptr;        // the r.rand stream (hb_set_rand), grown on demand
-  uint64_t rnd_cap = 0;
-  // hb_move_groups scratch, grown on demand and reused (capacities in u64 words)
-  uint64_t* mv_in = nullptr;      // the call's slot lists and vacated slots' extents (one H2D copy)
-  uint64_t mv_in_cap = 0;
-  uint64_t* mv_stage = nullptr;   // [move_words][count]
-  uint64_t mv_stage_cap = 0;
-  uint64_t* mv_jobs = nullptr;    // [count x nmax]
-  uint64_t mv_jobs_cap = 0;
-  uint64_t* mv_rstage = nullptr;  // the carried inflight windows
-  uint64_t mv_rstage_cap = 0;
-  unsigned long long* mv_ctr = nullptr;  // [2] jobs, ring-stage words
+  Dev<uint8_t> bin_key;           // [largest batch] key bytes of the tiled path
+  Dev<uint32_t> bin_hist;         // [256] bin totals, then [256][its tiles] tile histograms
+  Dev<uint32_t> enc_sum;          // hb_encode: [blocks] bytes per pass-one workgroup
+  Dev<uint64_t> enc_base;         // [blocks + 1]
+  Dev<uint64_t> rnd;              // the r.rand stream (hb_set_rand)
+  // hb_move_groups scratch, reused (u64 words)
+  Dev<uint64_t> mv_in;            // the call's slot lists and vacated slots' extents (one H2D copy)
+  Dev<uint64_t> mv_stage;         // [move_words][count]
+  Dev<uint64_t> mv_jobs;          // [count x nmax]
+  Dev<uint64_t> mv_rstage;        // the carried inflight windows
+  Dev<unsigned long long> mv_ctr;  // [2] jobs, ring-stage words
   std::vector<uint64_t> mv_host;  // host image of mv_in
   std::vector<uint8_t> mv_mark;   // [G] validation marks: 1 in src, 2 in dst (all zero between calls)
   static constexpr uint32_t PROF_RING = 256;
@@ -5056,15 +5080,10 @@ int reserve_log(hb_handle* h, uint32_t count, const uint32_t* groups, const uint
     }
   }
   const uint32_t nj = (uint32_t)(jobs.size() / 4);
-  if (h->lx_jobs_cap < jobs.size()) {
-    if (h->lx_jobs) (void)hipFree(h->lx_jobs);
-    h->lx_jobs = nullptr;
-    h->lx_jobs_cap = 0;
-    if (hipMalloc(&h->lx_jobs, jobs.size() * 8) != hipSuccess) return HB_ENOMEM;
-    h->lx_jobs_cap = jobs.size();
-  }
-  HB_CHECK(hipMemcpyAsync(h->lx_jobs, jobs.data(), jobs.size() * 8, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(k_regrow, dim3((nj + 255) / 256), dim3(256), 0, h->stream, h->st, nj, (const uint64_t*)h->lx_jobs);
+  if (const int rc = h->lx_jobs.reserve(jobs.size())) return rc;
+  HB_CHECK(hipMemcpyAsync(h->lx_jobs.get(), jobs.data(), jobs.size() * 8, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_regrow, dim3((nj + 255) / 256), dim3(256), 0, h->stream, h->st, nj,
+                     (const uint64_t*)h->lx_jobs.get());
   HB_CHECK(hipStreamSynchronize(h->stream));
   for (auto& o : old) h->pool.put(o.first, o.second);
   return HB_OK;
@@ -5110,18 +5129,18 @@ void egress_snapshot(hb_handle* h, hipStream_t st) {
   SnapArgs a;
   a.term = h->st.term;
   a.last = h->st.last;
-  a.term0 = h->term0;
-  a.last0 = h->last0;
+  a.term0 = h->term0.get();
+  a.last0 = h->last0.get();
   a.G = h->G;
   a.tfirst = h->st.tfirst;
   a.trx = h->st.trx;
   a.trc = h->st.trc;
-  a.lterm0 = h->lterm0;
+  a.lterm0 = h->lterm0.get();
   a.commit = h->st.commit;
   a.first = h->st.first;
-  a.commit0 = h->eg_commit0;
-  a.bl0 = h->bl0;
-  a.blt0 = h->blt0;
+  a.commit0 = h->eg_commit0.get();
+  a.bl0 = h->bl0.get();
+  a.blt0 = h->blt0.get();
   if (h->eg_apps) hipLaunchKernelGGL(k_eg_snap_app, dim3((h->G + 255) / 256), dim3(256), 0, st, a);
   else if (h->eg_votes) hipLaunchKernelGGL(k_eg_snap<true>, dim3((h->G + 511) / 512), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(k_eg_snap<false>, dim3((h->G + 511) / 512), dim3(256), 0, st, a);
@@ -5347,6 +5366,7 @@ int hb_create(int device, uint32_t capacity, uint32_t max_replicas, uint32_t max
   ALLOC(h->commit0, G);
   ALLOC(h->stats, HB_STAT_COUNT);
 #undef ALLOC
+  if (rc == HB_OK) rc = h->stats_pin.reserve(HB_STAT_COUNT);
   if (rc != HB_OK) {
     hb_destroy(h);
     return rc;
@@ -5357,8 +5377,7 @@ int hb_create(int device, uint32_t capacity, uint32_t max_replicas, uint32_t max
   (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
   bool ok = hipStreamCreateWithPriority(&h->prep, hipStreamNonBlocking, prio_least) == hipSuccess &&
             hipEventCreateWithFlags(&h->in_ready, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&h->hstage_done, hipEventDisableTiming) == hipSuccess &&
-            hipHostMalloc(reinterpret_cast<void**>(&h->stats_pin), HB_STAT_COUNT * 8, hipHostMallocDefault) == hipSuccess;
+            hipEventCreateWithFlags(&h->hstage_done, hipEventDisableTiming) == hipSuccess;
   for (PrepSet& ps : h->set)
     ok = ok && hipEventCreateWithFlags(&ps.prepped, hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&ps.applied, hipEventDisableTiming) == hipSuccess;
@@ -5403,9 +5422,6 @@ int hb_destroy(hb_handle* h) {
   if (!h) return HB_EINVAL;
   DeviceGuard guard(h->device);
   (void)hipDeviceSynchronize();
-  for (void* p : h->allocs) (void)hipFree(p);
-  h->pool.release();
-  if (h->lx_jobs) (void)hipFree(h->lx_jobs);
   for (auto& row : h->ph)
     for (auto& e : row)
       if (e) (void)hipEventDestroy(e);
@@ -5413,30 +5429,12 @@ int hb_destroy(hb_handle* h) {
     if (ps.prepped) (void)hipEventDestroy(ps.prepped);
     if (ps.applied) (void)hipEventDestroy(ps.applied);
   }
-  if (h->rnd) (void)hipFree(h->rnd);
-  for (void* p : {(void*)h->mv_in, (void*)h->mv_stage, (void*)h->mv_jobs, (void*)h->mv_rstage, (void*)h->mv_ctr})
-    if (p) (void)hipFree(p);
-  if (h->evx) (void)hipFree(h->evx);
-  if (h->evw) (void)hipFree(h->evw);
-  for (PrepSet& ps : h->set)
-    if (ps.dstage) (void)hipFree(ps.dstage);
-  if (h->hstage) (void)hipHostFree(h->hstage);
-  if (h->stats_pin) (void)hipHostFree(h->stats_pin);
   if (h->hstage_done) (void)hipEventDestroy(h->hstage_done);
-  if (h->s_edesc) (void)hipFree(h->s_edesc);
-  if (h->s_eterm) (void)hipFree(h->s_eterm);
-  if (h->peer) (void)hipFree(h->peer);
-  if (h->dec_q) (void)hipFree(h->dec_q);
-  if (h->dec_qn) (void)hipFree(h->dec_qn);
-  if (h->decf_sum) (void)hipFree(h->decf_sum);
-  if (h->decf_base) (void)hipFree(h->decf_base);
-  for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->lterm0, (void*)h->eg_commit0, (void*)h->bl0, (void*)h->blt0,
-                  (void*)h->eg_cnt, (void*)h->eg_base, (void*)h->enc_sum,
-                  (void*)h->enc_base, (void*)h->bin_table, (void*)h->bin_key, (void*)h->bin_hist})
-    if (p) (void)hipFree(p);
   if (h->in_ready) (void)hipEventDestroy(h->in_ready);
   if (h->prep) (void)hipStreamDestroy(h->prep);
-  delete h;
+  h->pool.release();
+  for (void* p : h->allocs) (void)hipFree(p);
+  delete h;  // every DevBuf member frees itself, on h->device still
   return HB_OK;
 }
 
@@ -5477,17 +5475,16 @@ int hb_load_groups(hb_handle* h, uint32_t first, uint32_t count, const hb_group*
     }
   }
   DeviceGuard guard(h->device);
-  hb_group* d = nullptr;
-  HB_CHECK(hipMalloc(&d, sizeof(hb_group) * count));
-  hipError_t e = hipMemcpyAsync(d, groups, sizeof(hb_group) * count, hipMemcpyHostToDevice, h->stream);
+  Dev<hb_group> d;
+  if (const int rc = d.reserve(count)) return rc;
+  hipError_t e = hipMemcpyAsync(d.get(), groups, sizeof(hb_group) * count, hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_load, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->st, first, count, d);
+    hipLaunchKernelGGL(k_load, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->st, first, count, d.get());
     if (h->peer)
-      hipLaunchKernelGGL(k_peer_n, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->peer, h->st.meta, first,
+      hipLaunchKernelGGL(k_peer_n, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->peer.get(), h->st.meta, first,
                          count);
     e = hipStreamSynchronize(h->stream);
   }
-  (void)hipFree(d);
   return e == hipSuccess ? HB_OK : HB_EDEVICE;
 }
 
@@ -5495,12 +5492,11 @@ int hb_get_groups(hb_handle* h, uint32_t first, uint32_t count, hb_group* out) {
   if (!h || !out || (uint64_t)first + count > h->G) return HB_EINVAL;
   if (count == 0) return HB_OK;
   DeviceGuard guard(h->device);
-  hb_group* d = nullptr;
-  HB_CHECK(hipMalloc(&d, sizeof(hb_group) * count));
-  hipLaunchKernelGGL(k_gather, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->st, first, count, d);
-  hipError_t e = hipMemcpyAsync(out, d, sizeof(hb_group) * count, hipMemcpyDeviceToHost, h->stream);
+  Dev<hb_group> d;
+  if (const int rc = d.reserve(count)) return rc;
+  hipLaunchKernelGGL(k_gather, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->st, first, count, d.get());
+  hipError_t e = hipMemcpyAsync(out, d.get(), sizeof(hb_group) * count, hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  (void)hipFree(d);
   return e == hipSuccess ? HB_OK : HB_EDEVICE;
 }
 
@@ -5510,18 +5506,6 @@ int hb_remove_groups(hb_handle* h, uint32_t first, uint32_t count) {
   DeviceGuard guard(h->device);
   hipLaunchKernelGGL(k_remove, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->st, first, count);
   HB_CHECK(hipStreamSynchronize(h->stream));
-  return HB_OK;
-}
-
-// a scratch buffer of at least `need` u64 words (the old one is idle: every call that uses it synchronizes)
-static int mv_grow(void** p, uint64_t* cap, uint64_t need) {
-  if (need <= *cap) return HB_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  const uint64_t want = std::max<uint64_t>(need, 2 * *cap);
-  *cap = 0;
-  if (hipMalloc(p, want * 8) != hipSuccess) return HB_ENOMEM;
-  *cap = want;
   return HB_OK;
 }
 
@@ -5557,13 +5541,14 @@ int hb_move_groups(hb_handle* h, uint32_t count, const uint32_t* src, const uint
   const bool sized = h->st.szx != nullptr;
 
   DeviceGuard guard(h->device);
-  const uint32_t NW = move_words(h->nmax, sized, h->peer != nullptr);
+  const uint32_t NW = move_words(h->nmax, sized, bool(h->peer));
   const uint64_t in_words = 2ull * nvac + (2ull * count + nvac + 1) / 2;
-  int rc = mv_grow(reinterpret_cast<void**>(&h->mv_in), &h->mv_in_cap, in_words);
-  if (rc == HB_OK) rc = mv_grow(reinterpret_cast<void**>(&h->mv_stage), &h->mv_stage_cap, (uint64_t)NW * count);
-  if (rc == HB_OK) rc = mv_grow(reinterpret_cast<void**>(&h->mv_jobs), &h->mv_jobs_cap, (uint64_t)h->nmax * count);
+  // the scratch at least doubles (the old blocks are idle: every call that uses them synchronizes)
+  int rc = h->mv_in.reserve(in_words, 2 * h->mv_in.cap());
+  if (rc == HB_OK) rc = h->mv_stage.reserve((uint64_t)NW * count, 2 * h->mv_stage.cap());
+  if (rc == HB_OK) rc = h->mv_jobs.reserve((uint64_t)h->nmax * count, 2 * h->mv_jobs.cap());
+  if (rc == HB_OK) rc = h->mv_ctr.reserve(2);
   if (rc != HB_OK) return rc;
-  if (!h->mv_ctr) HB_CHECK(hipMalloc(&h->mv_ctr, 16));
   // one upload: the vacated slots' new extent words (u64), then src, dst, vac (u32)
   h->mv_host.assign(in_words, 0);
   uint32_t* hsrc = reinterpret_cast<uint32_t*>(h->mv_host.data() + 2ull * nvac);
@@ -5577,31 +5562,31 @@ int hb_move_groups(hb_handle* h, uint32_t count, const uint32_t* src, const uint
   MoveArgs a{};
   a.count = count;
   a.nvac = nvac;
-  a.vac_szx = h->mv_in;
-  a.vac_trx = h->mv_in + nvac;
-  a.src = reinterpret_cast<const uint32_t*>(h->mv_in + 2ull * nvac);
+  a.vac_szx = h->mv_in.get();
+  a.vac_trx = h->mv_in.get() + nvac;
+  a.src = reinterpret_cast<const uint32_t*>(h->mv_in.get() + 2ull * nvac);
   a.dst = a.src + count;
   a.vac = a.dst + count;
-  a.stage = h->mv_stage;
-  a.peer = h->peer;
-  a.jobs = h->mv_jobs;
-  a.ctr = h->mv_ctr;
-  a.rstage = h->mv_rstage;
+  a.stage = h->mv_stage.get();
+  a.peer = h->peer.get();
+  a.jobs = h->mv_jobs.get();
+  a.ctr = h->mv_ctr.get();
+  a.rstage = h->mv_rstage.get();
   hipStream_t st = h->stream;
-  HB_CHECK(hipMemcpyAsync(h->mv_in, h->mv_host.data(), in_words * 8, hipMemcpyHostToDevice, st));
-  HB_CHECK(hipMemsetAsync(h->mv_ctr, 0, 16, st));
+  HB_CHECK(hipMemcpyAsync(h->mv_in.get(), h->mv_host.data(), in_words * 8, hipMemcpyHostToDevice, st));
+  HB_CHECK(hipMemsetAsync(h->mv_ctr.get(), 0, 16, st));
   hipLaunchKernelGGL(k_move_gather, dim3((count + 255) / 256), dim3(256), 0, st, h->st, a);
   HB_CHECK(hipGetLastError());
   // how many windows travel (none after a reset, the usual case: no ring kernels then)
   unsigned long long ctr[2] = {0, 0};
-  HB_CHECK(hipMemcpyAsync(ctr, h->mv_ctr, 16, hipMemcpyDeviceToHost, st));
+  HB_CHECK(hipMemcpyAsync(ctr, h->mv_ctr.get(), 16, hipMemcpyDeviceToHost, st));
   HB_CHECK(hipStreamSynchronize(st));
   const uint32_t njobs = (uint32_t)ctr[0];
   if (njobs) {
     if (ctr[0] > (uint64_t)h->nmax * count || ctr[1] > ctr[0] * h->W) return HB_EINVARIANT;
-    rc = mv_grow(reinterpret_cast<void**>(&h->mv_rstage), &h->mv_rstage_cap, ctr[1]);
+    rc = h->mv_rstage.reserve(ctr[1], 2 * h->mv_rstage.cap());
     if (rc != HB_OK) return rc;
-    a.rstage = h->mv_rstage;
+    a.rstage = h->mv_rstage.get();
     hipLaunchKernelGGL(k_move_ring<false>, dim3((njobs + 3) / 4), dim3(256), 0, st, h->st, a, njobs);
     HB_CHECK(hipGetLastError());
   }
@@ -5630,10 +5615,9 @@ int hb_set_log_bounds(hb_handle* h, uint32_t count, const uint32_t* groups, cons
   for (uint32_t i = 0; i < count; ++i)
     if (groups[i] >= h->G || first_index[i] == 0) return HB_EINVAL;
   DeviceGuard guard(h->device);
-  char* d = nullptr;
-  const size_t bytes = (size_t)count * (4 + 8 + 8);
-  HB_CHECK(hipMalloc(&d, bytes));
-  uint64_t* dfirst = reinterpret_cast<uint64_t*>(d);
+  Dev<char> d;
+  if (const int rc = d.reserve((uint64_t)count * (4 + 8 + 8))) return rc;
+  uint64_t* dfirst = reinterpret_cast<uint64_t*>(d.get());
   uint64_t* dsnap = dfirst + count;
   uint32_t* dgroup = reinterpret_cast<uint32_t*>(dsnap + count);
   hipError_t e = hipMemcpyAsync(dfirst, first_index, count * 8ull, hipMemcpyHostToDevice, h->stream);
@@ -5644,7 +5628,6 @@ int hb_set_log_bounds(hb_handle* h, uint32_t count, const uint32_t* groups, cons
                        (const uint32_t*)dgroup, (const uint64_t*)dfirst, (const uint64_t*)dsnap);
     e = hipStreamSynchronize(h->stream);
   }
-  (void)hipFree(d);
   return e == hipSuccess ? HB_OK : HB_EDEVICE;
 }
 
@@ -5662,12 +5645,10 @@ int hb_load_term_runs(hb_handle* h, uint32_t count, const uint32_t* groups, cons
   }
   if (tot && !runs) return HB_EINVAL;
   DeviceGuard guard(h->device);
-  const int rc = reserve_log(h, count, groups, nullptr, cap.data());
-  if (rc != HB_OK) return rc;
-  char* d = nullptr;
-  const size_t bytes = count * (8ull + 4 + 4) + tot * 16 + 16;
-  HB_CHECK(hipMalloc(&d, bytes));
-  uint64_t* doff = reinterpret_cast<uint64_t*>(d);
+  if (const int rc = reserve_log(h, count, groups, nullptr, cap.data())) return rc;
+  Dev<char> d;
+  if (const int rc = d.reserve(count * (8ull + 4 + 4) + tot * 16 + 16)) return rc;
+  uint64_t* doff = reinterpret_cast<uint64_t*>(d.get());
   uint64_t* druns = doff + count;
   uint32_t* dgrp = reinterpret_cast<uint32_t*>(druns + 2 * tot);
   uint32_t* dn = dgrp + count;
@@ -5680,7 +5661,6 @@ int hb_load_term_runs(hb_handle* h, uint32_t count, const uint32_t* groups, cons
                        (const uint32_t*)dgrp, (const uint32_t*)dn, (const uint64_t*)doff, (const uint64_t*)druns);
     e = hipStreamSynchronize(h->stream);
   }
-  (void)hipFree(d);
   return e == hipSuccess ? HB_OK : HB_EDEVICE;
 }
 
@@ -5699,12 +5679,10 @@ int hb_load_entry_sizes(hb_handle* h, uint32_t count, const uint32_t* groups, co
   }
   if (tot && !sizes) return HB_EINVAL;
   DeviceGuard guard(h->device);
-  const int rc = reserve_log(h, count, groups, cap.data(), nullptr);
-  if (rc != HB_OK) return rc;
-  char* d = nullptr;
-  const size_t bytes = count * (4ull + 4 + 8) + tot * 4 + 16;
-  HB_CHECK(hipMalloc(&d, bytes));
-  uint64_t* doff = reinterpret_cast<uint64_t*>(d);
+  if (const int rc = reserve_log(h, count, groups, cap.data(), nullptr)) return rc;
+  Dev<char> d;
+  if (const int rc = d.reserve(count * (4ull + 4 + 8) + tot * 4 + 16)) return rc;
+  uint64_t* doff = reinterpret_cast<uint64_t*>(d.get());
   uint32_t* dgrp = reinterpret_cast<uint32_t*>(doff + count);
   uint32_t* dn = dgrp + count;
   uint32_t* dsz = dn + count;
@@ -5717,7 +5695,6 @@ int hb_load_entry_sizes(hb_handle* h, uint32_t count, const uint32_t* groups, co
                        (const uint32_t*)dgrp, (const uint32_t*)dn, (const uint64_t*)doff, (const uint32_t*)dsz);
     e = hipStreamSynchronize(h->stream);
   }
-  (void)hipFree(d);
   return e == hipSuccess ? HB_OK : HB_EDEVICE;
 }
 
@@ -5741,15 +5718,14 @@ int hb_set_inflights(hb_handle* h, uint32_t group, uint32_t slot, uint32_t start
   if (!h || group >= h->G || slot >= h->nmax || start >= h->W || count > h->W || (count && !vals))
     return HB_EINVAL;
   DeviceGuard guard(h->device);
-  uint64_t* d = nullptr;
-  HB_CHECK(hipMalloc(&d, 8ull * (count ? count : 1)));
+  Dev<uint64_t> d;
+  if (const int rc = d.reserve(count ? count : 1)) return rc;
   hipError_t e = hipSuccess;
-  if (count) e = hipMemcpyAsync(d, vals, 8ull * count, hipMemcpyHostToDevice, h->stream);
+  if (count) e = hipMemcpyAsync(d.get(), vals, 8ull * count, hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_set_ins, dim3(1), dim3(256), 0, h->stream, h->st, group, slot, start, count, d);
+    hipLaunchKernelGGL(k_set_ins, dim3(1), dim3(256), 0, h->stream, h->st, group, slot, start, count, d.get());
     e = hipStreamSynchronize(h->stream);
   }
-  (void)hipFree(d);
   return e == hipSuccess ? HB_OK : HB_EDEVICE;
 }
 
@@ -5794,26 +5770,20 @@ int hb_set_rand(hb_handle* h, uint64_t first, uint64_t count, const uint64_t* dr
   if (!h || (count && !draws) || first > h->st.nrnd) return HB_EINVAL;  // no holes
   const uint64_t need = first + count;
   DeviceGuard guard(h->device);
-  if (need > h->rnd_cap) {
-    const uint64_t cap = need > 2 * h->rnd_cap ? need : 2 * h->rnd_cap;
-    uint64_t* p = nullptr;
-    HB_CHECK(hipMalloc(&p, cap * 8));
+  if (need > h->rnd.cap()) {  // the table at least doubles; the earlier draws move along
+    Dev<uint64_t> fresh;
+    if (const int rc = fresh.reserve(need, 2 * h->rnd.cap())) return rc;
     hipError_t e = hipSuccess;
-    if (h->rnd && first) e = hipMemcpyAsync(p, h->rnd, first * 8, hipMemcpyDeviceToDevice, h->stream);
+    if (h->rnd && first) e = hipMemcpyAsync(fresh.get(), h->rnd.get(), first * 8, hipMemcpyDeviceToDevice, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // no kernel reads the old table any more
-    if (e != hipSuccess) {
-      (void)hipFree(p);
-      return HB_EDEVICE;
-    }
-    if (h->rnd) (void)hipFree(h->rnd);
-    h->rnd = p;
-    h->rnd_cap = cap;
+    if (e != hipSuccess) return HB_EDEVICE;
+    h->rnd = std::move(fresh);
   }
   if (count) {
-    HB_CHECK(hipMemcpyAsync(h->rnd + first, draws, count * 8, hipMemcpyHostToDevice, h->stream));
+    HB_CHECK(hipMemcpyAsync(h->rnd.get() + first, draws, count * 8, hipMemcpyHostToDevice, h->stream));
     HB_CHECK(hipStreamSynchronize(h->stream));
   }
-  h->st.rnd = h->rnd;
+  h->st.rnd = h->rnd.get();
   if (need > h->st.nrnd) h->st.nrnd = need;
   return HB_OK;
 }
@@ -5824,19 +5794,56 @@ int hb_load_peers(hb_handle* h, uint32_t first, uint32_t count, const uint64_t* 
   DeviceGuard guard(h->device);
   const size_t G = h->G;
   if (!h->peer) {
-    HB_CHECK(hipMalloc(&h->peer, G * HB_PEER_ROW * 8));
-    HB_CHECK(hipMemsetAsync(h->peer, 0, G * HB_PEER_ROW * 8, h->stream));
+    if (const int rc = h->peer.reserve(G * HB_PEER_ROW)) return rc;
+    HB_CHECK(hipMemsetAsync(h->peer.get(), 0, G * HB_PEER_ROW * 8, h->stream));
   }
   // one 64-byte row per group (k_decode reads it with one gather): slots
   // 0..nmax-1, zeros, then n (k_peer_n)
   std::vector<uint64_t> rows((size_t)count * HB_PEER_ROW, 0);
   for (uint32_t i = 0; i < count; ++i)
     for (uint32_t s = 0; s < h->nmax; ++s) rows[(size_t)i * HB_PEER_ROW + s] = ids[(size_t)i * HB_MAX_REPLICAS + s];
-  HB_CHECK(hipMemcpyAsync(h->peer + (size_t)first * HB_PEER_ROW, rows.data(), rows.size() * 8, hipMemcpyHostToDevice,
-                          h->stream));
-  hipLaunchKernelGGL(k_peer_n, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->peer, h->st.meta, first, count);
+  HB_CHECK(hipMemcpyAsync(h->peer.get() + (size_t)first * HB_PEER_ROW, rows.data(), rows.size() * 8,
+                          hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_peer_n, dim3((count + 255) / 256), dim3(256), 0, h->stream, h->peer.get(), h->st.meta, first,
+                     count);
   HB_CHECK(hipGetLastError());
   HB_CHECK(hipStreamSynchronize(h->stream));  // rows is freed on return
+  return HB_OK;
+}
+
+// what hb_decode and hb_decode_follow hand their kernels alike
+static DecodeArgs decode_args(const hb_handle* h, const uint8_t* bytes, const uint64_t* off, const uint32_t* len,
+                              const uint32_t* group, uint64_t n, const hb_batch* out, uint8_t* status) {
+  DecodeArgs da;
+  da.bytes = bytes;
+  da.off = off;
+  da.len = len;
+  da.group = group;
+  da.n = n;
+  da.meta = h->st.meta;
+  da.peer = reinterpret_cast<const uint4*>(h->peer.get());
+  da.G = h->G;
+  da.nmax = h->nmax;
+  da.o_group = const_cast<uint32_t*>(out->group);
+  da.o_info = const_cast<uint32_t*>(out->info);
+  da.o_term = const_cast<uint64_t*>(out->term);
+  da.o_index = const_cast<uint64_t*>(out->index);
+  da.o_hint = const_cast<uint64_t*>(out->hint);
+  da.status = status;
+  return da;
+}
+// The pass-2 queue of both: room for n record indices, and its two counters
+// (zeroed on `ds` when they are allocated).  sync_first: wait for `ds` before
+// a queue that is too small is replaced.
+static int decode_queue(hb_handle* h, uint64_t n, hipStream_t ds, bool sync_first) {
+  if (n > h->dec_q.cap()) {
+    if (sync_first) HB_CHECK(hipStreamSynchronize(ds));
+    if (const int rc = h->dec_q.reserve(n)) return rc;
+  }
+  if (!h->dec_qn) {
+    if (const int rc = h->dec_qn.reserve(2)) return rc;
+    HB_CHECK(hipMemsetAsync(h->dec_qn.get(), 0, 2 * sizeof(uint32_t), ds));
+  }
   return HB_OK;
 }
 
@@ -5849,41 +5856,16 @@ int hb_decode(hb_handle* h, const uint8_t* bytes, const uint64_t* off, const uin
       !out->hint)
     return HB_EINVAL;
   DeviceGuard guard(h->device);
-  DecodeArgs da;
-  da.bytes = bytes;
-  da.off = off;
-  da.len = len;
-  da.group = group;
-  da.n = n;
-  da.meta = h->st.meta;
-  da.peer = reinterpret_cast<const uint4*>(h->peer);
-  da.G = h->G;
-  da.nmax = h->nmax;
-  da.o_group = const_cast<uint32_t*>(out->group);
-  da.o_info = const_cast<uint32_t*>(out->info);
-  da.o_term = const_cast<uint64_t*>(out->term);
-  da.o_index = const_cast<uint64_t*>(out->index);
-  da.o_hint = const_cast<uint64_t*>(out->hint);
-  da.status = status;
+  const DecodeArgs da = decode_args(h, bytes, off, len, group, n, out, status);
   // on the stream the batches come from, so hb_step's prep orders after it
   hipStream_t ds = h->in_stream_set ? h->in_stream : h->stream;
-  if (n > h->dec_cap) {  // the pass-2 queue holds up to n record indices
-    if (h->dec_q) (void)hipFree(h->dec_q);
-    h->dec_q = nullptr;
-    h->dec_cap = 0;
-    HB_CHECK(hipMalloc(&h->dec_q, n * sizeof(uint32_t)));
-    h->dec_cap = n;
-  }
-  if (!h->dec_qn) {
-    HB_CHECK(hipMalloc(&h->dec_qn, 2 * sizeof(uint32_t)));
-    HB_CHECK(hipMemsetAsync(h->dec_qn, 0, 2 * sizeof(uint32_t), ds));
-  }
+  if (const int rc = decode_queue(h, n, ds, false)) return rc;
   hipLaunchKernelGGL(k_decode, dim3((unsigned)((n + DEC_THREADS - 1) / DEC_THREADS)), dim3(DEC_THREADS), 0, ds, da,
-                     h->dec_q, h->dec_qn);
+                     h->dec_q.get(), h->dec_qn.get());
   HB_CHECK(hipGetLastError());
   const uint64_t gb = (n + DEC_THREADS - 1) / DEC_THREADS;
   hipLaunchKernelGGL(k_decode_general, dim3((unsigned)(gb < DEC_GEN_BLOCKS ? gb : DEC_GEN_BLOCKS)), dim3(DEC_THREADS), 0,
-                     ds, da, h->dec_q, h->dec_qn);
+                     ds, da, h->dec_q.get(), h->dec_qn.get());
   HB_CHECK(hipGetLastError());
   return HB_OK;
 }
@@ -5901,22 +5883,7 @@ int hb_decode_follow(hb_handle* h, const uint8_t* bytes, const uint64_t* off, co
   if (ent_cap && (!out->eterm || !out->edesc || !edata)) return HB_EINVAL;
   DeviceGuard guard(h->device);
   DecfArgs fa;
-  DecodeArgs& da = fa.d;
-  da.bytes = bytes;
-  da.off = off;
-  da.len = len;
-  da.group = group;
-  da.n = n;
-  da.meta = h->st.meta;
-  da.peer = reinterpret_cast<const uint4*>(h->peer);
-  da.G = h->G;
-  da.nmax = h->nmax;
-  da.o_group = const_cast<uint32_t*>(out->group);
-  da.o_info = const_cast<uint32_t*>(out->info);
-  da.o_term = const_cast<uint64_t*>(out->term);
-  da.o_index = const_cast<uint64_t*>(out->index);
-  da.o_hint = const_cast<uint64_t*>(out->hint);
-  da.status = status;
+  fa.d = decode_args(h, bytes, off, len, group, n, out, status);
   fa.o_commit = const_cast<uint64_t*>(out->commit);
   fa.eoff = const_cast<uint64_t*>(out->eoff);
   fa.eterm = const_cast<uint64_t*>(out->eterm);
@@ -5927,36 +5894,19 @@ int hb_decode_follow(hb_handle* h, const uint8_t* bytes, const uint64_t* off, co
   // on the stream the batches come from, as hb_decode
   hipStream_t ds = h->in_stream_set ? h->in_stream : h->stream;
   const uint64_t nblk = (n + DEC_THREADS - 1) / DEC_THREADS;
-  if (n > h->dec_cap) {  // the general pass's queue holds up to n record indices (shared with hb_decode)
+  if (const int rc = decode_queue(h, n, ds, true)) return rc;  // (shared with hb_decode)
+  if (nblk + 1 > h->decf_sum.cap()) {
     HB_CHECK(hipStreamSynchronize(ds));
-    if (h->dec_q) (void)hipFree(h->dec_q);
-    h->dec_q = nullptr;
-    h->dec_cap = 0;
-    HB_CHECK(hipMalloc(&h->dec_q, n * sizeof(uint32_t)));
-    h->dec_cap = n;
+    if (const int rc = reserve_pair(h->decf_sum, nblk + 1, h->decf_base, nblk + 2)) return rc;
   }
-  if (!h->dec_qn) {
-    HB_CHECK(hipMalloc(&h->dec_qn, 2 * sizeof(uint32_t)));
-    HB_CHECK(hipMemsetAsync(h->dec_qn, 0, 2 * sizeof(uint32_t), ds));
-  }
-  if (nblk + 1 > h->decf_cap) {
-    HB_CHECK(hipStreamSynchronize(ds));
-    if (h->decf_sum) (void)hipFree(h->decf_sum);
-    if (h->decf_base) (void)hipFree(h->decf_base);
-    h->decf_sum = nullptr;
-    h->decf_base = nullptr;
-    h->decf_cap = 0;
-    HB_CHECK(hipMalloc(&h->decf_sum, (nblk + 1) * sizeof(uint32_t)));
-    HB_CHECK(hipMalloc(&h->decf_base, (nblk + 2) * sizeof(uint64_t)));
-    h->decf_cap = nblk + 1;
-  }
-  fa.bsum = h->decf_sum;
-  fa.bbase = h->decf_base;
+  fa.bsum = h->decf_sum.get();
+  fa.bbase = h->decf_base.get();
   if (nblk) {
-    hipLaunchKernelGGL(k_decf_parse, dim3((unsigned)nblk), dim3(DEC_THREADS), 0, ds, fa, h->dec_q, h->dec_qn);
+    hipLaunchKernelGGL(k_decf_parse, dim3((unsigned)nblk), dim3(DEC_THREADS), 0, ds, fa, h->dec_q.get(),
+                       h->dec_qn.get());
     HB_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_decf_general, dim3((unsigned)(nblk < DEC_GEN_BLOCKS ? nblk : DEC_GEN_BLOCKS)), dim3(DEC_THREADS),
-                       0, ds, fa, h->dec_q, h->dec_qn);
+                       0, ds, fa, h->dec_q.get(), h->dec_qn.get());
     HB_CHECK(hipGetLastError());
   }
   if (n <= DECF_SMALL_MAX && !h->no_small) {
@@ -6007,22 +5957,16 @@ int hb_get_inflights(hb_handle* h, uint32_t group, uint32_t slot, uint32_t* star
                      uint64_t* vals) {
   if (!h || group >= h->G || slot >= h->nmax || !start || !count || !vals) return HB_EINVAL;
   DeviceGuard guard(h->device);
-  uint64_t* d = nullptr;
-  uint32_t* sc = nullptr;
-  HB_CHECK(hipMalloc(&d, 8ull * h->W));
-  if (hipMalloc(&sc, 8) != hipSuccess) {
-    (void)hipFree(d);
-    return HB_EDEVICE;
-  }
-  hipLaunchKernelGGL(k_get_ins, dim3(1), dim3(256), 0, h->stream, h->st, group, slot, d, sc);
+  Dev<uint64_t> d;
+  Dev<uint32_t> sc;
+  if (reserve_pair(d, h->W, sc, 2) != HB_OK) return HB_ENOMEM;
+  hipLaunchKernelGGL(k_get_ins, dim3(1), dim3(256), 0, h->stream, h->st, group, slot, d.get(), sc.get());
   uint32_t hsc[2] = {0, 0};
-  hipError_t e = hipMemcpyAsync(hsc, sc, 8, hipMemcpyDeviceToHost, h->stream);
+  hipError_t e = hipMemcpyAsync(hsc, sc.get(), 8, hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e == hipSuccess && hsc[1]) e = hipMemcpy(vals, d, 8ull * hsc[1], hipMemcpyDeviceToHost);
+  if (e == hipSuccess && hsc[1]) e = hipMemcpy(vals, d.get(), 8ull * hsc[1], hipMemcpyDeviceToHost);
   *start = hsc[0];
   *count = hsc[1];
-  (void)hipFree(d);
-  (void)hipFree(sc);
   return e == hipSuccess ? HB_OK : HB_EDEVICE;
 }
 
@@ -6095,28 +6039,20 @@ int hb_step(hb_handle* h, const hb_batch* b, uint32_t flags) {
     }
     if (total > 0 && total <= STAGE_MAX) {
       packed = true;
-      if (total > h->hstage_cap) {
+      // both blocks are STAGE_MAX bytes from their first use
+      int rc = h->hstage.reserve(total, STAGE_MAX, [h]() -> int {
         HB_CHECK(hipEventSynchronize(h->hstage_done));
-        if (h->hstage) (void)hipHostFree(h->hstage);
-        h->hstage = nullptr;
-        h->hstage_cap = 0;
-        HB_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h->hstage), STAGE_MAX, hipHostMallocDefault));
-        h->hstage_cap = STAGE_MAX;
-      }
-      if (total > ps.dstage_cap) {  // (this set's last reader is done: the prep stream waited for it)
-        HB_CHECK(hipStreamSynchronize(st));
-        if (ps.dstage) (void)hipFree(ps.dstage);
-        ps.dstage = nullptr;
-        ps.dstage_cap = 0;
-        HB_CHECK(hipMalloc(reinterpret_cast<void**>(&ps.dstage), STAGE_MAX));
-        ps.dstage_cap = STAGE_MAX;
-      }
+        return HB_OK;
+      });
+      // (this set's last reader is done: the prep stream waited for it)
+      if (rc == HB_OK) rc = ps.dstage.reserve(total, STAGE_MAX, stream_idle(st));
+      if (rc != HB_OK) return rc;
       HB_CHECK(hipEventSynchronize(h->hstage_done));  // the previous step's copy has left the block
       for (const Part& q : parts)
-        if (q.src && q.bytes) std::memcpy(h->hstage + q.off, q.src, q.bytes);
-      HB_CHECK(hipMemcpyAsync(ps.dstage, h->hstage, total, hipMemcpyHostToDevice, ps_st));
+        if (q.src && q.bytes) std::memcpy(h->hstage.get() + q.off, q.src, q.bytes);
+      HB_CHECK(hipMemcpyAsync(ps.dstage.get(), h->hstage.get(), total, hipMemcpyHostToDevice, ps_st));
       HB_CHECK(hipEventRecord(h->hstage_done, ps_st));
-      auto at = [&](int k) { return parts[k].src && parts[k].bytes ? ps.dstage + parts[k].off : nullptr; };
+      auto at = [&](int k) { return parts[k].src && parts[k].bytes ? ps.dstage.get() + parts[k].off : nullptr; };
       bd.group = reinterpret_cast<const uint32_t*>(at(0));
       bd.info = reinterpret_cast<const uint32_t*>(at(1));
       bd.term = reinterpret_cast<const uint64_t*>(at(2));
@@ -6149,29 +6085,20 @@ int hb_step(hb_handle* h, const hb_batch* b, uint32_t flags) {
     bd.hint = b->hint ? h->s_hint : nullptr;
     bd.props = b->props ? h->s_props : nullptr;
     // entry descriptors / terms, m.Commit: read by apply, so on the apply stream
-    auto grow = [&](auto** p, uint64_t* cap, uint64_t need, size_t elem) -> int {
-      if (need <= *cap) return HB_OK;
-      HB_CHECK(hipStreamSynchronize(st));  // the old staging may still be read
-      if (*p) (void)hipFree(*p);
-      *p = nullptr;
-      *cap = 0;
-      HB_CHECK(hipMalloc(reinterpret_cast<void**>(p), need * elem));
-      *cap = need;
-      return HB_OK;
-    };
+    // (the old staging may still be read: the apply stream goes idle before it is replaced)
     if (sized && b->edesc && b->n_edesc) {
-      if (grow(&h->s_edesc, &h->s_edesc_cap, b->n_edesc, 4) != HB_OK) return HB_EDEVICE;
-      HB_CHECK(hipMemcpyAsync(h->s_edesc, b->edesc, b->n_edesc * 4, hipMemcpyHostToDevice, st));
+      if (const int rc = h->s_edesc.reserve(b->n_edesc, 0, stream_idle(st))) return rc;
+      HB_CHECK(hipMemcpyAsync(h->s_edesc.get(), b->edesc, b->n_edesc * 4, hipMemcpyHostToDevice, st));
     }
     if (b->eterm && b->n_edesc) {
-      if (grow(&h->s_eterm, &h->s_eterm_cap, b->n_edesc, 8) != HB_OK) return HB_EDEVICE;
-      HB_CHECK(hipMemcpyAsync(h->s_eterm, b->eterm, b->n_edesc * 8, hipMemcpyHostToDevice, st));
+      if (const int rc = h->s_eterm.reserve(b->n_edesc, 0, stream_idle(st))) return rc;
+      HB_CHECK(hipMemcpyAsync(h->s_eterm.get(), b->eterm, b->n_edesc * 8, hipMemcpyHostToDevice, st));
     }
     if (b->eoff && n) HB_CHECK(hipMemcpyAsync(h->s_eoff, b->eoff, n * 8, hipMemcpyHostToDevice, st));
     if (b->commit && n) HB_CHECK(hipMemcpyAsync(h->s_commit, b->commit, n * 8, hipMemcpyHostToDevice, st));
     if (sized && b->props) HB_CHECK(hipMemcpyAsync(h->s_peoff, b->peoff, (size_t)h->G * 8, hipMemcpyHostToDevice, st));
-    bd_edesc = (sized && b->edesc) ? h->s_edesc : nullptr;
-    bd_eterm = b->eterm ? h->s_eterm : nullptr;
+    bd_edesc = (sized && b->edesc) ? h->s_edesc.get() : nullptr;
+    bd_eterm = b->eterm ? h->s_eterm.get() : nullptr;
     bd_eoff = b->eoff ? h->s_eoff : nullptr;
     bd_commit = b->commit ? h->s_commit : nullptr;
     bd_peoff = (sized && b->props) ? h->s_peoff : nullptr;
@@ -6373,23 +6300,16 @@ int hb_events_device(hb_handle* h, const uint64_t** base, const uint64_t** chunk
 int hb_copy_events(hb_handle* h, hb_event* out, uint64_t cap, uint64_t* n) {
   if (!h || !n) return HB_EINVAL;
   DeviceGuard guard(h->device);
-  HB_CHECK(hipMemcpyAsync(h->stats_pin, h->stats, HB_STAT_COUNT * 8, hipMemcpyDeviceToHost, h->stream));
+  HB_CHECK(hipMemcpyAsync(h->stats_pin.get(), h->stats, HB_STAT_COUNT * 8, hipMemcpyDeviceToHost, h->stream));
   HB_CHECK(hipStreamSynchronize(h->stream));
-  const uint64_t total = h->stepped ? h->stats_pin[HB_STAT_EVENTS] : 0;
+  const uint64_t total = h->stepped ? h->stats_pin.get()[HB_STAT_EVENTS] : 0;
   *n = total;
   if (total == 0) return HB_OK;
   if (!out || cap < total) return HB_EINVAL;
-  // expansion scratch (records + per-chunk scan), kept across calls and grown on demand
+  // expansion scratch (records + per-chunk scan), kept across calls; it grows with a quarter to spare
   const uint64_t need = total * sizeof(hb_event) + 24ull * h->NB;
-  if (need > h->evx_cap) {
-    if (h->evx) (void)hipFree(h->evx);
-    h->evx = nullptr;
-    h->evx_cap = 0;
-    const uint64_t cap = need + need / 4;
-    HB_CHECK(hipMalloc(&h->evx, cap));
-    h->evx_cap = cap;
-  }
-  hb_event* d = reinterpret_cast<hb_event*>(h->evx);
+  if (const int rc = h->evx.reserve(need, need + need / 4)) return rc;
+  hb_event* d = reinterpret_cast<hb_event*>(h->evx.get());
   uint64_t* dst = reinterpret_cast<uint64_t*>(d + total);
   uint32_t* per_chunk = reinterpret_cast<uint32_t*>(dst + 2 * h->NB);
   hipLaunchKernelGGL(k_chunk_events, dim3(2 * h->NB), dim3(256), 0, h->stream, (const uint64_t*)h->ev,
@@ -6415,13 +6335,7 @@ int hb_events_to_host(hb_handle* h, uint64_t* words, uint64_t cap, uint32_t* cou
     HB_CHECK(hipMemsetAsync(dt, 0, 8, h->stream));
     return HB_OK;
   }
-  if (h->evw_cap < nc + 1ull) {
-    if (h->evw) (void)hipFree(h->evw);
-    h->evw = nullptr;
-    h->evw_cap = 0;
-    HB_CHECK(hipMalloc(&h->evw, (nc + 1ull) * 8));
-    h->evw_cap = nc + 1ull;
-  }
+  if (const int rc = h->evw.reserve(nc + 1ull)) return rc;
   const PrepSet& ps = h->set[h->cur];
   if (nc <= WORDS_SMALL && !h->no_small) {
     hipLaunchKernelGGL(k_words_small, dim3(1), dim3(1024), 0, h->stream, (const uint32_t*)ps.ev_counts, nc,
@@ -6429,35 +6343,30 @@ int hb_events_to_host(hb_handle* h, uint64_t* words, uint64_t cap, uint32_t* cou
                        static_cast<uint32_t*>(dc), static_cast<uint64_t*>(dt));
     return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
   }
-  hipLaunchKernelGGL(k_scan_words, dim3(1), dim3(1024), 0, h->stream, (const uint32_t*)ps.ev_counts, nc, h->evw,
+  hipLaunchKernelGGL(k_scan_words, dim3(1), dim3(1024), 0, h->stream, (const uint32_t*)ps.ev_counts, nc, h->evw.get(),
                      static_cast<uint32_t*>(dc), static_cast<uint64_t*>(dt));
   hipLaunchKernelGGL(k_gather_words, dim3(nc), dim3(256), 0, h->stream, (const uint64_t*)h->ev,
-                     (const uint32_t*)ps.ev_counts, (const uint64_t*)ps.ev_off, (const uint64_t*)h->evw,
+                     (const uint32_t*)ps.ev_counts, (const uint64_t*)ps.ev_off, (const uint64_t*)h->evw.get(),
                      static_cast<uint64_t*>(dw), cap);
   return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
 }
 
 // ---- wire egress ---------------------------------------------------------------
 // the snapshot columns of a mode: lterm0 in vote and append mode, commit0 / bl0 / blt0 in append mode
-static void egress_free_cols(hb_handle* h, bool lt, bool apps) {
-  if (lt && h->lterm0) (void)hipFree(h->lterm0);
-  if (lt) h->lterm0 = nullptr;
-  if (!apps) return;
-  for (void* p : {(void*)h->eg_commit0, (void*)h->bl0, (void*)h->blt0})
-    if (p) (void)hipFree(p);
-  h->eg_commit0 = h->bl0 = h->blt0 = nullptr;
+static int egress_reserve_cols(hb_handle* h, bool lt, bool apps) {
+  const uint64_t G = h->G;
+  int rc = lt ? h->lterm0.reserve(G) : HB_OK;
+  for (Dev<uint64_t>* c : {&h->eg_commit0, &h->bl0, &h->blt0})
+    if (apps && rc == HB_OK) rc = c->reserve(G);
+  return rc;
 }
-static bool egress_alloc_cols(hb_handle* h, bool lt, bool apps) {
-  const size_t G = h->G;
-  if (lt && !h->lterm0 && hipMalloc(&h->lterm0, G * 8) != hipSuccess) {
-    h->lterm0 = nullptr;
-    return false;
-  }
-  if (apps && !h->eg_commit0 &&
-      (hipMalloc(&h->eg_commit0, G * 8) != hipSuccess || hipMalloc(&h->bl0, G * 8) != hipSuccess ||
-       hipMalloc(&h->blt0, G * 8) != hipSuccess))
-    return false;
-  return true;
+// only a mode's own columns stay
+static void egress_keep_cols(hb_handle* h, bool lt, bool apps) {
+  if (!lt) h->lterm0.release();
+  if (apps) return;
+  h->eg_commit0.release();
+  h->bl0.release();
+  h->blt0.release();
 }
 int hb_set_egress(hb_handle* h, int on) {
   if (!h) return HB_EINVAL;
@@ -6465,39 +6374,41 @@ int hb_set_egress(hb_handle* h, int on) {
   const bool votes = on && (on & HB_EGRESS_VOTES), apps = on && (on & HB_EGRESS_APPS);
   if (h->egress && (!on || votes != h->eg_votes || apps != h->eg_apps))
     HB_CHECK(hipStreamSynchronize(h->stream));  // an hb_egress may still read the columns
+  auto drop_all = [h] {
+    h->term0.release();
+    h->last0.release();
+    h->eg_cnt.release();
+    h->eg_base.release();
+    egress_keep_cols(h, false, false);
+  };
   if (!on) {
     if (!h->egress) return HB_OK;
-    for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->eg_cnt, (void*)h->eg_base})
-      if (p) (void)hipFree(p);
-    egress_free_cols(h, true, true);
-    h->term0 = h->last0 = h->eg_base = nullptr;
-    h->eg_cnt = nullptr;
+    drop_all();
     h->egress = h->eg_votes = h->eg_apps = false;
     return HB_OK;
   }
-  const size_t G = h->G, nc = 2 * (size_t)h->NB;
+  const uint64_t G = h->G, nc = 2 * (uint64_t)h->NB;
   if (h->egress) {
     if (votes == h->eg_votes && apps == h->eg_apps) return HB_OK;
     // the mode changes: the step before this call has no matching snapshot
     h->eg_stepped = false;
-    if (!egress_alloc_cols(h, votes || apps, apps)) {  // (the mode in force stays; nothing new is kept)
-      egress_free_cols(h, !(h->eg_votes || h->eg_apps), !h->eg_apps);
-      return HB_ENOMEM;
+    if (const int rc = egress_reserve_cols(h, votes || apps, apps)) {  // (the mode in force stays; nothing new is kept)
+      egress_keep_cols(h, h->eg_votes || h->eg_apps, h->eg_apps);
+      return rc;
     }
-    egress_free_cols(h, !(votes || apps), !apps);
+    egress_keep_cols(h, votes || apps, apps);  // (the new columns exist: the old mode's others go)
     h->eg_votes = votes;
     h->eg_apps = apps;
     return HB_OK;
   }
-  if (hipMalloc(&h->term0, G * 8) != hipSuccess || hipMalloc(&h->last0, G * 8) != hipSuccess ||
-      hipMalloc(&h->eg_cnt, nc * 4) != hipSuccess || hipMalloc(&h->eg_base, (nc + 1) * 8) != hipSuccess ||
-      !egress_alloc_cols(h, votes || apps, apps)) {
-    for (void* p : {(void*)h->term0, (void*)h->last0, (void*)h->eg_cnt, (void*)h->eg_base})
-      if (p) (void)hipFree(p);
-    egress_free_cols(h, true, true);
-    h->term0 = h->last0 = h->eg_base = nullptr;
-    h->eg_cnt = nullptr;
-    return HB_ENOMEM;
+  int rc = h->term0.reserve(G);
+  if (rc == HB_OK) rc = h->last0.reserve(G);
+  if (rc == HB_OK) rc = h->eg_cnt.reserve(nc);
+  if (rc == HB_OK) rc = h->eg_base.reserve(nc + 1);
+  if (rc == HB_OK) rc = egress_reserve_cols(h, votes || apps, apps);
+  if (rc != HB_OK) {
+    drop_all();
+    return rc;
   }
   h->egress = true;
   h->eg_votes = votes;
@@ -6533,16 +6444,16 @@ int hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t 
   ea.ev_counts = ps.ev_counts;
   ea.nc = 2 * h->NB;
   ea.G = h->G;
-  ea.term0 = h->term0;
-  ea.last0 = h->last0;
-  ea.peer = h->peer;
-  ea.lterm0 = h->lterm0;
-  ea.commit0 = h->eg_commit0;
-  ea.bl0 = h->bl0;
-  ea.blt0 = h->blt0;
+  ea.term0 = h->term0.get();
+  ea.last0 = h->last0.get();
+  ea.peer = h->peer.get();
+  ea.lterm0 = h->lterm0.get();
+  ea.commit0 = h->eg_commit0.get();
+  ea.bl0 = h->bl0.get();
+  ea.blt0 = h->blt0.get();
   ea.max_msg_size = h->max_msg_size;
-  ea.ccnt = h->eg_cnt;
-  ea.cbase = h->eg_base;
+  ea.ccnt = h->eg_cnt.get();
+  ea.cbase = h->eg_base.get();
   ea.cap = cap;
   ea.count = dcount;
   ea.o_group = out->group;
@@ -6607,15 +6518,10 @@ int hb_encode(hb_handle* h, const hb_out_batch* in, uint64_t cap, const uint64_t
   if (!h->enc_sum) {  // once, for the largest batch the handle takes
     const uint64_t cm = cap_max * WO_MAX >= (1ull << 32) ? ((1ull << 32) - 1) / WO_MAX : cap_max;
     const uint64_t nb = (cm + ENC_THREADS - 1) / ENC_THREADS + 1;
-    if (hipMalloc(&h->enc_sum, nb * 4) != hipSuccess) return HB_ENOMEM;
-    if (hipMalloc(&h->enc_base, (nb + 1) * 8) != hipSuccess) {
-      (void)hipFree(h->enc_sum);
-      h->enc_sum = nullptr;
-      return HB_ENOMEM;
-    }
+    if (const int rc = reserve_pair(h->enc_sum, nb, h->enc_base, nb + 1)) return rc;
   }
-  ea.bsum = h->enc_sum;
-  ea.bbase = h->enc_base;
+  ea.bsum = h->enc_sum.get();
+  ea.bbase = h->enc_base.get();
   const uint32_t nblk = (uint32_t)((cap + ENC_THREADS - 1) / ENC_THREADS);
   if (nblk == 0) {  // (cap 0 with the small path off)
     hipLaunchKernelGGL(k_enc_small, dim3(1), dim3(ENC_SMALL_THREADS), 0, h->stream, ea);
@@ -6636,20 +6542,15 @@ int hb_set_egress_peers(hb_handle* h, const uint64_t* ids, uint32_t n) {
   if (n == 0) {
     if (!h->bin_table) return HB_OK;
     HB_CHECK(hipStreamSynchronize(h->stream));  // an hb_egress_bin may still read them
-    for (void* p : {(void*)h->bin_table, (void*)h->bin_key, (void*)h->bin_hist})
-      if (p) (void)hipFree(p);
-    h->bin_table = nullptr;
-    h->bin_key = nullptr;
-    h->bin_hist = nullptr;
+    h->bin_table.release();
+    h->bin_key.release();
+    h->bin_hist.release();
     h->bin_np = 0;
     return HB_OK;
   }
-  if (!h->bin_table && hipMalloc(&h->bin_table, sizeof(BinTable)) != hipSuccess) {
-    h->bin_table = nullptr;
-    return HB_ENOMEM;
-  }
+  if (const int rc = h->bin_table.reserve(1)) return rc;
   // on the stream, after the hb_egress_bin calls made so far; `t` lives on this stack
-  HB_CHECK(hipMemcpyAsync(h->bin_table, &t, sizeof(BinTable), hipMemcpyHostToDevice, h->stream));
+  HB_CHECK(hipMemcpyAsync(h->bin_table.get(), &t, sizeof(BinTable), hipMemcpyHostToDevice, h->stream));
   HB_CHECK(hipStreamSynchronize(h->stream));
   h->bin_np = n;
   return HB_OK;
@@ -6690,7 +6591,7 @@ int hb_egress_bin(hb_handle* h, const hb_out_batch* in, uint64_t cap, const uint
   a.o_hint = out->hint;
   a.src = src;
   a.bin_off = dev_view(bin_off);
-  a.table = h->bin_table;
+  a.table = h->bin_table.get();
   a.np = h->bin_np;
   a.cap = (uint32_t)cap;
   a.n_dev = dev_view(n_dev);
@@ -6705,20 +6606,12 @@ int hb_egress_bin(hb_handle* h, const hb_out_batch* in, uint64_t cap, const uint
   if (!h->bin_key) {  // once, for the largest batch the handle takes
     const uint64_t cm = std::min<uint64_t>(h->max_batch * (h->nmax + 4ull), (1ull << 32) - 1);
     const uint64_t nt = (cm + BIN_TILE - 1) / BIN_TILE;
-    if (hipMalloc(&h->bin_key, cm) != hipSuccess) {
-      h->bin_key = nullptr;
-      return HB_ENOMEM;
-    }
-    if (hipMalloc(&h->bin_hist, (nt + 1) * BIN_SLOTS * 4) != hipSuccess) {  // the bins' totals, then their rows
-      (void)hipFree(h->bin_key);
-      h->bin_key = nullptr;
-      h->bin_hist = nullptr;
-      return HB_ENOMEM;
-    }
+    // (the bins' totals, then their rows)
+    if (const int rc = reserve_pair(h->bin_key, cm, h->bin_hist, (nt + 1) * BIN_SLOTS)) return rc;
   }
-  a.key = h->bin_key;
-  a.tot = h->bin_hist;
-  a.hist = h->bin_hist + BIN_SLOTS;
+  a.key = h->bin_key.get();
+  a.tot = h->bin_hist.get();
+  a.hist = h->bin_hist.get() + BIN_SLOTS;
   a.ntiles = (uint32_t)((cap + BIN_TILE - 1) / BIN_TILE);
   hipLaunchKernelGGL(k_bin_hist, dim3(a.ntiles), dim3(BIN_THREADS), 0, h->stream, a);
   hipLaunchKernelGGL(k_bin_scan, dim3(a.np + 1), dim3(1024), 0, h->stream, a);
