@@ -2830,7 +2830,8 @@ __global__ void __launch_bounds__(PART, 2) k_tick(ApplyArgs a) {
     // Progress resumed.  Only those fields are read and only a cleared pause bit
     // is written (Lane::step would load the whole group, ring heads included,
     // and write every peer's Progress back unchanged).  The self slot, whose
-    // arrays may be stale under M_SM, is skipped.
+    // arrays may be stale under M_SM, is skipped; Next, which may be stale under
+    // M_NX, is not read.
     const uint64_t committed = a.S.commit[g];
     const uint32_t nn = L.n(), sf = L.self();
     uint64_t mt[NMAX];
@@ -3393,6 +3394,9 @@ __global__ void k_load(DevState S, uint32_t first, uint32_t count, const hb_grou
   if (r.self_slot < r.n && r.pr[r.self_slot].match == r.last_index && r.pr[r.self_slot].next == r.last_index + 1)
     m |= M_SM;
   if (r.commit_zero && r.committed != 0) m |= M_NC;  // r.Commit = 0 until the group's first Step
+  bool nx = S.lazy_next != 0 && r.state == HB_STATE_LEADER && r.n != 0 && r.n <= S.nmax;
+  for (uint32_t s = 0; s < S.nmax && s < r.n; ++s) nx = nx && r.pr[s].next == r.last_index + 1;
+  if (nx) m |= M_NX;  // the next words are then not kept (nor written here)
   S.meta[g] = m;
   S.elapsed[g] = 0;  // newRaft: fresh r.rand, becomeFollower -> reset
   S.rpos[g] = 0;
@@ -3405,7 +3409,7 @@ __global__ void k_load(DevState S, uint32_t first, uint32_t count, const hb_grou
     const bool on = s < r.n;
     const size_t o = (size_t)s * S.G + g;
     S.match[o] = on ? r.pr[s].match : 0;
-    S.next[o] = on ? r.pr[s].next : 0;
+    if (!(nx && on)) S.next[o] = on ? r.pr[s].next : 0;
     S.pending[o] = on ? r.pr[s].pending_snapshot : 0;
     S.pm[o] = on ? pm_make(r.pr[s].state, r.pr[s].paused, r.pr[s].ins_start, r.pr[s].ins_count) : 0;
   }
@@ -3439,7 +3443,7 @@ __global__ void k_gather(DevState S, uint32_t first, uint32_t count, hb_group* d
     uint32_t p = S.pm[o];
     const bool kept = !((m & M_SM) && s == r.self_slot);  // M_SM: materialized from last
     r.pr[s].match = kept ? S.match[o] : r.last_index;
-    r.pr[s].next = kept ? S.next[o] : r.last_index + 1;
+    r.pr[s].next = (kept && !(m & M_NX)) ? S.next[o] : r.last_index + 1;  // M_NX: every slot's, likewise
     if (m & M_RS) rs_progress(m, s, r.last_index, r.term_first, &r.pr[s].match, &r.pr[s].next, &p);
     r.pr[s].state = pm_state(p);
     r.pr[s].paused = pm_paused(p);
@@ -3448,6 +3452,14 @@ __global__ void k_gather(DevState S, uint32_t first, uint32_t count, hb_group* d
     r.pr[s].pending_snapshot = pm_state(p) == HB_PR_SNAPSHOT ? S.pending[o] : 0;
   }
   dst[i] = r;
+}
+
+// hb_lazy_next_groups (tests): the live groups whose next array is not kept (M_NX)
+__global__ void k_count_lazy_next(DevState S, uint32_t* out) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t m = g < S.G ? S.meta[g] : 0ull;
+  const uint64_t b = __ballot(m_n(m) != 0 && (m & M_NX) != 0);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(out, (uint32_t)__popcll(b));
 }
 
 __global__ void k_set_bounds(DevState S, uint32_t count, const uint32_t* groups, const uint64_t* first,
@@ -3546,6 +3558,7 @@ __global__ void k_set_ins(DevState S, uint32_t g, uint32_t s, uint32_t start, ui
       }
       S.meta[g] = m & ~M_RS;
     }
+    // (M_NX stays as it is: a window is not Next, and the flag never comes with M_RS)
     const size_t o = (size_t)s * S.G + g;
     const uint32_t p = S.pm[o];
     S.pm[o] = pm_make(pm_state(p), pm_paused(p), start, count);
@@ -3572,7 +3585,7 @@ __global__ void k_get_ins(DevState S, uint32_t g, uint32_t s, uint64_t* vals, ui
 // sources are read (k_move_gather, k_move_ring<false>) into a staging buffer
 // before any destination is written (k_move_scatter, k_move_ring<true>), so
 // swaps, cycles and chains need no ordering.  The raw words travel: the lazy
-// forms of meta (M_RS / M_SM / M_TL / M_NC) stay exactly as they are.
+// forms of meta (M_RS / M_SM / M_TL / M_NC / M_NX) stay exactly as they are.
 // ============================================================================
 struct MoveArgs {
   uint32_t count, nvac;
@@ -5260,6 +5273,8 @@ int hb_create(int device, uint32_t capacity, uint32_t max_replicas, uint32_t max
   s.G = capacity;
   s.W = max_inflight;
   s.nmax = h->nmax;
+  s.lazy_next = h->nmax <= 3 ? 1u : 0u;  // M_NX (hipbatch_kernels.h); HB_LAZY_NEXT=0: never set (same output)
+  if (const char* e = getenv("HB_LAZY_NEXT")) s.lazy_next = (h->nmax <= 3 && atoi(e) != 0) ? 1u : 0u;
   s.max_msg_size = max_msg_size;
   int rc = HB_OK;
 #define ALLOC(ptr, count) \
@@ -6718,6 +6733,19 @@ int hb_steady_waves(hb_handle* h, uint32_t* n) {
   DeviceGuard guard(h->device);
   HB_CHECK(hipStreamSynchronize(h->stream));
   HB_CHECK(hipMemcpy(n, h->set[h->cur].ctr + CTR_STEADY, 4, hipMemcpyDeviceToHost));
+  return HB_OK;
+}
+
+int hb_lazy_next_groups(hb_handle* h, uint32_t* n) {
+  if (!h || !n) return HB_EINVAL;
+  *n = 0;
+  DeviceGuard guard(h->device);
+  Dev<uint32_t> d;
+  if (const int rc = d.reserve(1)) return rc;
+  HB_CHECK(hipMemsetAsync(d.get(), 0, 4, h->stream));
+  hipLaunchKernelGGL(k_count_lazy_next, dim3((h->G + 255) / 256), dim3(256), 0, h->stream, h->st, d.get());
+  HB_CHECK(hipMemcpyAsync(n, d.get(), 4, hipMemcpyDeviceToHost, h->stream));
+  HB_CHECK(hipStreamSynchronize(h->stream));
   return HB_OK;
 }
 

@@ -89,8 +89,10 @@ struct ElectLane {
     // and its pauses (a leader with peers sent to them); otherwise they are written out
     const bool leader = state() == HB_STATE_LEADER;
     const bool rs = rst && (leader ? (tfirst == rlast + 1 && (sent || nn <= 1)) : (rlast == last && !sent));
-    const uint64_t m2 = (meta & ~(M_TL | M_SM | M_RS)) | (tl ? M_TL : 0ull) | (sm ? M_SM : 0ull) |
-                        (rs ? M_RS : (rst ? 0ull : (meta & M_RS)));
+    // (M_NX: no group this lane steps carries it — on an n = 3 handle it steps only a non-leader's MsgHup
+    // (k_tick), and n >= 5 handles never set it — but whatever writes M_RS clears it: a reset rewrites Next)
+    const uint64_t m2 = (meta & ~(M_TL | M_SM | M_RS | (rst ? M_NX : 0ull))) | (tl ? M_TL : 0ull) |
+                        (sm ? M_SM : 0ull) | (rs ? M_RS : (rst ? 0ull : (meta & M_RS)));
     if (m2 != meta) {
       meta = m2;
       dirty |= D_META;

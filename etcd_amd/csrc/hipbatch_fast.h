@@ -94,15 +94,16 @@ struct FastLane {
   // ... and those that wait for meta (which arrays are kept) and pm (the ring
   // heads): the second round trip.
   __device__ __forceinline__ void load_rest() {
-    // arrays the meta flags mark as not kept are not read (M_TL / M_SM,
+    // arrays the meta flags mark as not kept are not read (M_TL / M_SM / M_NX,
     // hipbatch_kernels.h); these loads issue once meta is in, beside the
     // ring heads, which wait for pm anyway
     tlast = (mlo & (uint32_t)M_TL) ? last : at32(S.tlast, g);
     const uint32_t sf = (mlo & (uint32_t)M_SM) ? self() : 0xFFu;
+    const bool nxl = NMAX <= 3 && (mlo & (uint32_t)M_NX) != 0;  // (slots >= n are never read)
 #pragma unroll
     for (int s = 0; s < NMAX; ++s) {
       match[s] = ((uint32_t)s == sf) ? last : at32(S.match, s * S.G + g);
-      next[s] = ((uint32_t)s == sf) ? last + 1 : at32(S.next, s * S.G + g);
+      next[s] = ((uint32_t)s == sf || nxl) ? last + 1 : at32(S.next, s * S.G + g);
     }
     if (mlo & (uint32_t)M_RS) {  // a group k_elect left in the reset form: every slot written back
       const uint32_t nn = n();
@@ -161,6 +162,26 @@ struct FastLane {
         dirty |= D_META | (1u << (D_SLOT0 + s0));
       }
     }
+    // M_NX is derived again (the lane is a Leader past the M_RS form, and stays
+    // one): set while every slot's Next == last + 1, and the next array is then
+    // not written; a flag that falls makes the array live, so every slot's is
+    bool nx = false;
+    if constexpr (NMAX <= 3) {
+      const uint32_t nn = n();
+      nx = S.lazy_next != 0 && state() == HB_STATE_LEADER && nn != 0;
+#pragma unroll
+      for (int s = 0; s < NMAX; ++s)
+        if ((uint32_t)s < nn) nx = nx && next[s] == last + 1;
+      if (nx != ((mlo & (uint32_t)M_NX) != 0)) {
+        if (!nx) {
+#pragma unroll
+          for (int s = 0; s < NMAX; ++s)
+            if ((uint32_t)s < nn) dirty |= 1u << (D_SLOT0 + s);
+        }
+        mlo ^= (uint32_t)M_NX;
+        dirty |= D_META;
+      }
+    }
     if (dirty & D_META) at32(reinterpret_cast<uint32_t*>(S.meta), 2 * g) = mlo;  // little-endian low word
     if (dirty & D_COMMIT) at32(S.commit, g) = committed;
     if (dirty & D_LAST) at32(S.last, g) = last;
@@ -170,7 +191,7 @@ struct FastLane {
     for (int s = 0; s < NMAX; ++s) {
       if ((dirty & (1u << (D_SLOT0 + s))) && (uint32_t)s != sf) {
         at32(S.match, s * S.G + g) = match[s];
-        at32(S.next, s * S.G + g) = next[s];
+        if (!nx) at32(S.next, s * S.G + g) = next[s];
       }
       if (dirty & (1u << (D_PM0 + s))) at32(S.pm, s * S.G + g) = pm[s];
     }
@@ -552,6 +573,12 @@ struct SteadyLane {
     fb.next = isa ? bn : nx;
     fb.pm = isa ? bp : p;
     touch_b = touch_b || !isa;
+    // the window this ack leaves is empty, so an inflights.add made earlier in
+    // the step for this follower lies outside it: nothing reads that ring word
+    // (only [start, start + count) is ever read), and it is not stored.  A later
+    // send of the step sets add / ring afresh.
+    add_a = add_a && !isa;
+    add_b = add_b && isa;
     if (maybe_commit(term, first, EW_P + 2 * t)) bcast(W, first, EW_P + 2 * t + 1);
   }
 
@@ -627,32 +654,34 @@ struct SteadyLane {
     return evc_word(EVC_BCAST, (1u << sa) | (1u << sb), (ltm >> j) & 1u, lane, j == jfirst ? xfirst : last, false);
   }
 
-  // FastLane::store for what plan() changed (meta never changes: M_TL and
-  // M_SM, where set, still hold, so their arrays stay unwritten).
+  // FastLane::store for what plan() changed.  M_TL and M_SM, where set, still
+  // hold, so their arrays stay unwritten and those bits never change.  M_NX is
+  // derived as FastLane::store does (a steady step nearly always ends with
+  // every Next at last + 1): while it holds no Next is written; the one meta
+  // store is for a group that gains it (or, a follower left behind without a
+  // bcastAppend, loses it: then all three Next words are written).
   __device__ __forceinline__ void commit(const FastLane<3>& L) const {
     const DevState& S = L.S;
     const uint32_t g = L.g;
+    const bool nx0 = (L.mlo & (uint32_t)M_NX) != 0;
+    const bool nx = S.lazy_next != 0 && snext == last + 1 && fa.next == last + 1 && fb.next == last + 1;
+    const bool all = nx0 && !nx;  // the next array is live again
+    if (nx != nx0) at32(reinterpret_cast<uint32_t*>(S.meta), 2 * g) = L.mlo ^ (uint32_t)M_NX;
     if (committed != L.committed) at32(S.commit, g) = committed;
     if (prop) {
       at32(S.last, g) = last;
       if (d_tfirst) at32(S.tfirst, g) = tfirst;
       if (!(L.mlo & (uint32_t)M_TL)) at32(S.tlast, g) = tlast;
-      if (!(L.mlo & (uint32_t)M_SM)) {
-        at32(S.match, sf * S.G + g) = smatch;
-        at32(S.next, sf * S.G + g) = snext;
-      }
+      if (!(L.mlo & (uint32_t)M_SM)) at32(S.match, sf * S.G + g) = smatch;
     }
+    if (!(L.mlo & (uint32_t)M_SM) && !nx && (prop || all)) at32(S.next, sf * S.G + g) = snext;
     if (spm != spm0) at32(S.pm, sf * S.G + g) = spm;
-    if (touch_a) {
-      at32(S.match, sa * S.G + g) = fa.match;
-      at32(S.next, sa * S.G + g) = fa.next;
-    }
+    if (touch_a) at32(S.match, sa * S.G + g) = fa.match;
+    if (!nx && (touch_a || all)) at32(S.next, sa * S.G + g) = fa.next;
     if (fa.pm != pa0) at32(S.pm, sa * S.G + g) = fa.pm;
     if (add_a) *L.ring_at(sa, ring_a) = last;
-    if (touch_b) {
-      at32(S.match, sb * S.G + g) = fb.match;
-      at32(S.next, sb * S.G + g) = fb.next;
-    }
+    if (touch_b) at32(S.match, sb * S.G + g) = fb.match;
+    if (!nx && (touch_b || all)) at32(S.next, sb * S.G + g) = fb.next;
     if (fb.pm != pb0) at32(S.pm, sb * S.G + g) = fb.pm;
     if (add_b) *L.ring_at(sb, ring_b) = last;
   }

@@ -142,6 +142,8 @@ struct FollowLane : Base {
     }
     const uint64_t ne = rec_ne(info), lastnewi = index + ne;
     if (ne) {  // maybeAppend: every entry is past the log's end (no conflict scan), all at Term
+      // (M_NX, the other form derived from lastIndex, is never set here: takes_follow admits only a
+      // Follower, and only a Leader carries that flag — the store that ends a leadership clears it)
       if (mlo & (uint32_t)M_SM) {  // the self Match / Next were derived from lastIndex: pin them
         self_last = last;
         mlo &= ~(uint32_t)M_SM;

@@ -31,7 +31,7 @@ constexpr uint32_t CHUNK = 4 * PART;         // messages staged in LDS per round
 
 // ---- packed group meta (u64) ------------------------------------------------
 //  [0:2) state  [2:5) n  [5:9) self slot  [9:13) lead ref  [13:17) vote ref
-//  [17:21) fault  [21] M_TL  [22] M_SM  [23] M_RS  [24] M_NC
+//  [17:21) fault  [21] M_TL  [22] M_SM  [23] M_RS  [24] M_NC  [25] M_NX
 //  [32:40) votes granted  [40:48) votes responded
 //  (the flags every lane tests sit in the low word, which the fast lanes load
 //  and store alone; the vote tally, read only by the election lanes, is above)
@@ -68,6 +68,22 @@ constexpr uint64_t M_RS = 1ull << 23;
 // lane (Lane::step) steps such a group: every specialised lane hands it over,
 // and Lane::step clears the flag once the message passes the gate.
 constexpr uint64_t M_NC = 1ull << 24;
+// M_NX: every slot s < n has Next == lastIndex + 1 — the next array is then
+// not kept for this group.  A leader's Replicate follower with no size limit is
+// left so by every bcastAppend (optimisticUpdate, raft/raft.go:270-273), and an
+// ack keeps it (max(Next, Index + 1) with Index <= lastIndex), so a healthy
+// leader holds it at every step boundary, also while acks lag its proposals.
+// Only on handles with nmax <= 3 (DevState::lazy_next; HB_LAZY_NEXT=0 at
+// hb_create: never), only on a Leader, never together with M_RS (whatever
+// writes M_RS clears it).  k_load sets it; the n = 3 lanes that hold Progress
+// (FastLane<3>, SteadyLane, Lane<3, *>) derive it again at store; every other
+// reader of next materializes last + 1 (k_gather).  A lane that moves lastIndex
+// without Progress loaded pins first (Lane::follower_append); FollowLane steps
+// only Followers, which never carry it, and a Leader leaves that state only
+// through Lane::transition, whose reset() loads Progress, so the store that
+// writes the new state clears the flag and writes every slot.  On handles with
+// nmax >= 5 it is never set: LeadLane, LeadLaneL and k_elect do not know it.
+constexpr uint64_t M_NX = 1ull << 25;
 __host__ __device__ inline uint32_t m_state(uint64_t m) { return (uint32_t)(m & 3); }
 __host__ __device__ inline uint32_t m_n(uint64_t m) { return (uint32_t)((m >> 2) & 7); }
 __host__ __device__ inline uint32_t m_self(uint64_t m) { return (uint32_t)((m >> 5) & 0xF); }
@@ -104,7 +120,7 @@ struct DevState {
   uint32_t G;                 // group capacity
   uint32_t W;                 // MaxInflightMsgs
   uint32_t nmax;              // max replicas of this handle
-  uint32_t pad;
+  uint32_t lazy_next;         // 1: M_NX may be set (nmax <= 3 and not HB_LAZY_NEXT=0), 0: never
   uint64_t max_msg_size;      // HB_NO_LIMIT or 0
   uint64_t* term;             // [G] HardState.Term
   uint64_t* commit;           // [G] raftLog.committed
@@ -493,10 +509,12 @@ struct Lane {
     prog = false;
   }
   __device__ __forceinline__ void load_progress() {
+    // M_NX as loaded: the next array is stale, last (unchanged so far) + 1 is every slot's value
+    const bool nxl = NMAX <= 3 && (meta0 & M_NX) != 0;
 #pragma unroll
     for (int s = 0; s < NMAX; ++s) {
       match[s] = S.match[(size_t)s * S.G + g];
-      next[s] = S.next[(size_t)s * S.G + g];
+      next[s] = nxl ? ((uint32_t)s < n() ? last + 1 : 0ull) : S.next[(size_t)s * S.G + g];
       pm[s] = S.pm[(size_t)s * S.G + g];
     }
     if (meta & M_RS) {  // the reset form (every slot rewritten by store)
@@ -533,7 +551,8 @@ struct Lane {
 
   __device__ __forceinline__ void store() {
     if (dirty & D_FIRST) S.first[g] = first;  // a restored snapshot
-    {  // re-derive M_TL / M_SM; an array that was stale and no longer may be is written
+    bool nx;
+    {  // re-derive M_TL / M_SM / M_NX; an array that was stale and no longer may be is written
       const uint32_t sf = self(), nn = n();
       const bool tl = tlast == last;
       bool sm = (meta0 & M_SM) != 0;  // progress never loaded: nothing (incl. last) changed it
@@ -543,13 +562,27 @@ struct Lane {
         for (int s = 0; s < NMAX; ++s)
           if ((uint32_t)s == sf && (uint32_t)s < nn) sm = match[s] == last && next[s] == last + 1;
       }
-      const uint64_t m2 = (meta & ~(M_TL | M_SM)) | (tl ? M_TL : 0ull) | (sm ? M_SM : 0ull);
+      // M_NX: a Leader (not in the reset form) whose every slot has Next == last + 1
+      nx = NMAX <= 3 && (meta0 & M_NX) != 0;  // progress never loaded: nothing (incl. last, the state) changed it
+      if (NMAX <= 3 && prog) {
+        nx = S.lazy_next != 0 && state() == HB_STATE_LEADER && nn != 0 && !(meta & M_RS);
+#pragma unroll
+        for (int s = 0; s < NMAX; ++s)
+          if ((uint32_t)s < nn) nx = nx && next[s] == last + 1;
+      }
+      const uint64_t m2 =
+          (meta & ~(M_TL | M_SM | M_NX)) | (tl ? M_TL : 0ull) | (sm ? M_SM : 0ull) | (nx ? M_NX : 0ull);
       if (m2 != meta) {
         meta = m2;
         dirty |= D_META;
       }
       if (!tl && (meta0 & M_TL)) dirty |= D_TRUN;
       if (!sm && (meta0 & M_SM) && sf < (uint32_t)NMAX) dirty |= 1u << (D_SLOT0 + sf);
+      if (!nx && (meta0 & M_NX)) {  // the next array is live again: every slot's is written
+#pragma unroll
+        for (int s = 0; s < NMAX; ++s)
+          if ((uint32_t)s < nn) dirty |= 1u << (D_SLOT0 + s);
+      }
     }
     if (dirty & D_META) S.meta[g] = meta;
     if (dirty & D_TERM) S.term[g] = term;
@@ -564,7 +597,7 @@ struct Lane {
     for (int s = 0; s < NMAX; ++s) {
       if (dirty & (1u << (D_SLOT0 + s))) {
         S.match[(size_t)s * S.G + g] = match[s];
-        S.next[(size_t)s * S.G + g] = next[s];
+        if (!nx) S.next[(size_t)s * S.G + g] = next[s];
         S.pm[(size_t)s * S.G + g] = pm[s];
       }
     }
@@ -803,7 +836,7 @@ struct Lane {
   // (maybeAppend raft/log.go:80-85 -> unstable.truncateAndAppend): the log is
   // cut at ci - 1 and takes entries ci .. index + ne (terms eterm[e0 ..]).
   __device__ __forceinline__ void follower_append(uint64_t ci, uint64_t index, uint64_t e0, uint64_t ne) {
-    if (!prog) load_progress();  // M_SM derives the self Match from last: pin it before last moves
+    if (!prog) load_progress();  // M_SM / M_NX derive Match / Next from last: pin them before last moves
     Runs rr;
     rr.open(S, g);
     rr.cut(ci);

@@ -571,6 +571,15 @@ class Engine:
         _check("hb_steady_waves", f(self.h, C.byref(n)))
         return int(n.value)
 
+    def lazy_next_groups(self):
+        """hb_lazy_next_groups: live groups whose Next array is not kept (every
+        slot's Next == lastIndex + 1; never with HB_LAZY_NEXT=0 at create)."""
+        f = lib().hb_lazy_next_groups  # (bound here: an A/B build from before the form has no such symbol)
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]
+        n = C.c_uint32()
+        _check("hb_lazy_next_groups", f(self.h, C.byref(n)))
+        return int(n.value)
+
     def phase_ms(self):
         """(per-phase average ms, number of profiled steps) since phase_reset()."""
         out = np.zeros(abi.HB_PHASE_COUNT, dtype=np.float32)

@@ -846,6 +846,15 @@ int  hb_step_kernels(hb_handle* h, uint32_t* mask);
  * count, 0 when the knob was not set (synchronizes). */
 int  hb_steady_waves(hb_handle* h, uint32_t* n);
 
+/* On handles with max_replicas <= 3 the engine does not keep the per-slot Next
+ * of a leader whose every slot has Next == lastIndex + 1 (what bcastAppend's
+ * optimistic update leaves a healthy leader with at every step boundary): the
+ * steady step neither reads nor writes those words, and hb_get_groups derives
+ * them.  HB_LAZY_NEXT=0 at hb_create turns that off (same output).  For
+ * tests: *n = the live groups currently held in that form (synchronizes);
+ * always 0 with HB_LAZY_NEXT=0 or max_replicas > 3. */
+int  hb_lazy_next_groups(hb_handle* h, uint32_t* n);
+
 /* ---- pinned host memory for cgo callers (Go must not hand Go memory to C
  * that C retains; raft/hipbatch packs batches into these buffers). -------- */
 int  hb_alloc_pinned(size_t bytes, void** out);
