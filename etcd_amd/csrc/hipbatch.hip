@@ -3451,6 +3451,9 @@ __global__ void k_gather(DevState S, uint32_t first, uint32_t count, hb_group* d
     r.pr[s].ins_count = pm_count(p);
     r.pr[s].pending_snapshot = pm_state(p) == HB_PR_SNAPSHOT ? S.pending[o] : 0;
   }
+  // the record's run lies in [first_index - 1, last_index]: hb_set_log_bounds may have moved
+  // firstIndex past the start the device keeps (which M_RS above still needs as it is)
+  if (r.term_first != HB_NO_INDEX && r.term_first + 1 < r.first_index) r.term_first = r.first_index - 1;
   dst[i] = r;
 }
 

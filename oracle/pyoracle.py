@@ -111,6 +111,9 @@ class orc_raft(C.Structure):
     ]
 
 
+ERR_COMPACTED, ERR_SNAP_OUT_OF_DATE, ERR_OUT_OF_BOUND = 1, 2, -1  # orc_log_compact (raft/storage.go:172-214)
+
+
 def build():
     """Compile the oracle with its Makefile (gcc)."""
     subprocess.run(["make", "-s", "-C", _HERE], check=True)
@@ -194,6 +197,9 @@ def lib():
                                                C.c_uint64, P(C.c_uint64)]),
             "orc_raft_handle_append_entries": (None, [R, P(orc_msg)]),
             "orc_raft_handle_heartbeat": (None, [R, P(orc_msg)]),
+            "orc_log_compact": (C.c_int, [P(orc_log), C.c_uint64, C.c_int]),
+            "orc_raft_compact": (C.c_int, [R, C.c_uint64, C.c_int]),
+            "orc_groups_compact": (None, [R, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -451,6 +457,11 @@ class Raft:
     def q(self):
         return lib().orc_raft_q(C.byref(self.r))
 
+    def compact(self, i, snapshot=False):
+        """storage.CreateSnapshot(i, ...) when `snapshot`, then storage.Compact(i)
+        (raft/storage.go:172-214): 0, ERR_COMPACTED, ERR_SNAP_OUT_OF_DATE or ERR_OUT_OF_BOUND."""
+        return lib().orc_raft_compact(C.byref(self.r), i, int(snapshot))
+
     def to_group(self):
         g = abi.hb_group()
         lib().orc_raft_to_group(C.byref(self.r), C.byref(g))
@@ -481,6 +492,7 @@ class OracleGroups:
         L = lib()
         self.G = len(groups)
         self.max_inflight = max_inflight
+        self.max_msg_size = max_msg_size
         self.ptr = L.orc_groups_new(self.G)
         gbuf = np.ascontiguousarray(groups, dtype=abi.GROUP_DTYPE)
         flat, off = flat_runs(runs)
@@ -586,6 +598,29 @@ class OracleGroups:
             a = (C.c_uint64 * max(1, 2 * len(rr)))(*[x for r in rr for x in r])
             if L.orc_raft_load_term_runs(L.orc_groups_at(self.ptr, g), len(rr), a) != 0:
                 raise ValueError(f"orc_raft_load_term_runs(group {g}) failed")
+
+    def reload(self, g, record, runs):
+        """Group g is removed and created anew from an engine record and its log term
+        runs (hb_remove_groups + hb_load_groups: no entry size, no older term run)."""
+        L = lib()
+        r = L.orc_groups_at(self.ptr, g)
+        L.orc_raft_free(r)
+        rec = np.ascontiguousarray(record, dtype=abi.GROUP_DTYPE).reshape(1)
+        rr = (orc_run * len(runs))(*[orc_run(int(i), int(t)) for i, t in runs])
+        rc = L.orc_raft_from_group(r, C.cast(rec.ctypes.data, C.POINTER(abi.hb_group)), rr, len(runs),
+                                   self.max_inflight, self.max_msg_size)
+        if rc != 0:
+            raise ValueError(f"orc_raft_from_group({g}) failed: {rc}")
+
+    def compact(self, groups, index, snap=True):
+        """The application compacts groups[k] at index[k] (MemoryStorage.CreateSnapshot
+        where snap[k], then Compact; raft/storage.go:172-214).  Returns the int32 codes."""
+        g = np.ascontiguousarray(groups, dtype=np.uint32)
+        i = np.ascontiguousarray(np.broadcast_to(np.asarray(index, dtype=np.uint64), g.shape))
+        sn = np.ascontiguousarray(np.broadcast_to(np.asarray(snap, dtype=np.uint8), g.shape))
+        rc = np.zeros(len(g), dtype=np.int32)
+        lib().orc_groups_compact(self.ptr, self.G, len(g), g.ctypes.data, i.ctypes.data, sn.ctypes.data, rc.ctypes.data)
+        return rc
 
     def term(self, g, i):
         """raftLog.term(i) of group g (the oracle's whole log)."""

@@ -195,6 +195,28 @@ uint64_t orc_log_find_conflict(const orc_log* l, uint64_t from, const uint64_t* 
   return 0;
 }
 
+/* The application's side of the log: MemoryStorage.CreateSnapshot(i) when
+ * make_snapshot (raft/storage.go:172-191), then MemoryStorage.Compact(i)
+ * (raft/storage.go:196-214), as raftLog sees them through firstIndex(),
+ * term() and snapshot().  The entry i becomes the dummy entry and keeps its
+ * term (:209-210), so runs[0].index == first_index - 1 still holds. */
+int orc_log_compact(orc_log* l, uint64_t i, int make_snapshot) {
+  if (make_snapshot) {
+    if (i <= l->snap_index) return ORC_ERR_SNAP_OUT_OF_DATE;   /* :175-177 */
+    if (i > l->last_index) return ORC_ERR_OUT_OF_BOUND;        /* Panicf :180-182 */
+    l->snap_index = i;                                         /* :184 (its term is term(i), :185) */
+  }
+  if (i <= l->first_index - 1) return ORC_ERR_COMPACTED;       /* :199-202 (offset = ents[0].Index) */
+  if (i > l->last_index) return ORC_ERR_OUT_OF_BOUND;          /* Panicf :203-205 */
+  int k = 0;                                                   /* the run that holds i */
+  while (k + 1 < l->nruns && l->runs[k + 1].index <= i) k++;
+  if (k > 0) memmove(l->runs, l->runs + k, sizeof(orc_run) * (size_t)(l->nruns - k));
+  l->nruns -= k;
+  l->runs[0].index = i;                                        /* ents[0] = {Index: i, Term: term(i)} :208-210 */
+  l->first_index = i + 1;                                      /* firstIndex() = ents[0].Index + 1 :145-147 */
+  return 0;
+}
+
 int orc_log_is_up_to_date(const orc_log* l, uint64_t lasti, uint64_t term) {  /* :235-237 */
   uint64_t lt = orc_log_last_term(l);
   return term > lt || (term == lt && lasti >= l->last_index);
@@ -359,7 +381,10 @@ void orc_raft_commit_to(orc_raft* r, uint64_t tocommit) { /* commitTo raft/log.g
 /* ---- what the engine's log index knows of the terms (follower side) ----
  * The engine's term runs hold every run the caller loaded (hb_load_term_runs)
  * plus the ones its own appends / resets started; the harness reserves ring
- * capacity so none is dropped (hb_reserve_log).  All the oracle tracks is
+ * capacity (hb_reserve_log) so none that reaches into [first_index - 1,
+ * last_index] is dropped (tests/compact_util.py holds the rings at that span,
+ * so runs wholly below a compacted first_index - 1 do leave; tw_lo then names
+ * a run the engine no longer holds, which no lookup can reach).  All the oracle tracks is
  * the oldest run start the engine knows (tw_lo) and its current-term run; the
  * terms themselves come from `log`. */
 static void tw_push(orc_raft* r, uint64_t start, uint64_t term) {
@@ -1405,6 +1430,27 @@ void orc_groups_export_timers(const orc_raft* gs, uint32_t n, hb_timer* out) {
     out[i].rand_pos = (uint32_t)gs[i].rand_pos;
     out[i].election_tick = (uint16_t)gs[i].election_timeout;
     out[i].heartbeat_tick = (uint16_t)gs[i].heartbeat_timeout;
+  }
+}
+
+/* CreateSnapshot + Compact on a raft's log.  What the engine's log index
+ * knows (sz_lo, tw_lo, tw_tfirst) stays: nothing below first_index - 1 is
+ * read again (sendAppend sends a snapshot for Next < firstIndex, raft/raft.go:
+ * 246-260; raftLog.term is 0 below the dummy entry, raft/log.go:198-204). */
+int orc_raft_compact(orc_raft* r, uint64_t compact_index, int make_snapshot) {
+  return orc_log_compact(&r->log, compact_index, make_snapshot);
+}
+
+/* groups[k] compacts at index[k] (snap[k] != 0: after CreateSnapshot); rc[k] as
+ * orc_raft_compact.  A removed (n == 0) group answers ORC_ERR_COMPACTED. */
+void orc_groups_compact(orc_raft* gs, uint32_t ngroups, uint32_t count, const uint32_t* groups,
+                        const uint64_t* index, const uint8_t* snap, int32_t* rc) {
+  for (uint32_t k = 0; k < count; k++) {
+    if (groups[k] >= ngroups || gs[groups[k]].n == 0) {
+      rc[k] = ORC_ERR_COMPACTED;
+      continue;
+    }
+    rc[k] = orc_raft_compact(&gs[groups[k]], index[k], snap ? snap[k] : 1);
   }
 }
 

@@ -126,7 +126,9 @@ typedef struct orc_raft {
    * = the oldest index whose size the caller loaded into the engine's log
    * index (hb_load_entry_sizes), mirrored so that the engine precondition
    * HB_FAULT_SIZE_WINDOW is checked too; the harness reserves ring capacity
-   * (hb_reserve_log), so the engine drops nothing the oracle keeps. */
+   * (hb_reserve_log) for [first_index - 1, last_index] at least, so the engine
+   * drops nothing the oracle can read (what lies below a compacted
+   * first_index - 1 may leave the ring; sz_lo is not moved for it). */
   uint64_t* szc;
   uint64_t szc_base, szc_n, szc_cap, sz_lo;
   /* What the engine's log index knows of the terms (follower side; the terms
@@ -166,6 +168,12 @@ void     orc_log_free(orc_log* l);
 void     orc_log_push(orc_log* l, uint64_t term, uint64_t k);    /* append k entries of term */
 uint64_t orc_log_term(const orc_log* l, uint64_t i);
 uint64_t orc_log_last_term(const orc_log* l);
+/* MemoryStorage.CreateSnapshot(i) (when make_snapshot) then Compact(i)
+ * (raft/storage.go:172-214): 0, or the reference's error / panic */
+#define ORC_ERR_COMPACTED         1   /* ErrCompacted: i <= first_index - 1 (raft/storage.go:200-202) */
+#define ORC_ERR_SNAP_OUT_OF_DATE  2   /* ErrSnapOutOfDate: i <= snap_index (raft/storage.go:175-177) */
+#define ORC_ERR_OUT_OF_BOUND    (-1)  /* Panicf "... is out of bound lastindex" (:180-182, 203-205) */
+int      orc_log_compact(orc_log* l, uint64_t i, int make_snapshot);
 
 /* ---- raft ---- */
 /* newRaft (raft/raft.go:157-209) with Config peers; the log must be set up
@@ -211,6 +219,9 @@ void orc_raft_campaign(orc_raft* r);
 int  orc_raft_poll(orc_raft* r, uint64_t id, int v);
 void orc_raft_step(orc_raft* r, const orc_msg* m);
 void orc_raft_commit_to(orc_raft* r, uint64_t tocommit);
+/* the application compacts its Storage (raft/storage.go:172-214, see orc_log_compact);
+ * sz_lo / tw_lo / tw_tfirst are left as they are */
+int  orc_raft_compact(orc_raft* r, uint64_t compact_index, int make_snapshot);
 /* readMessages (raft/raft_test.go:44-49): copies up to cap, clears, returns count */
 int  orc_raft_read_messages(orc_raft* r, orc_msg* out, int cap);
 
@@ -269,6 +280,9 @@ int       orc_groups_load(orc_raft* gs, uint32_t n, const hb_group* recs, const 
 void      orc_groups_export(const orc_raft* gs, uint32_t n, hb_group* out);
 /* per group out[4i..4i+3] = log term runs, sz_lo (oldest loaded size), first_index, last_index */
 void      orc_groups_log_info(const orc_raft* gs, uint32_t n, uint64_t* out);
+/* groups[k] compacts at index[k], after CreateSnapshot where snap[k] != 0 (NULL: all); rc[k] as orc_raft_compact */
+void      orc_groups_compact(orc_raft* gs, uint32_t ngroups, uint32_t count, const uint32_t* groups,
+                             const uint64_t* index, const uint8_t* snap, int32_t* rc);
 orc_raft* orc_groups_at(orc_raft* g, uint32_t i);
 size_t    orc_sizeof_raft(void);
 

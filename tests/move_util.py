@@ -82,6 +82,13 @@ class SlotView:
     def reserve_log(self, groups, size_cap=None, run_cap=None):
         return self.real.reserve_log(self.slot[np.asarray(groups, dtype=np.int64)].astype(np.uint32), size_cap, run_cap)
 
+    def set_log_bounds(self, groups, first_index, snap_index):
+        return self.real.set_log_bounds(self.slot[np.asarray(groups, dtype=np.int64)].astype(np.uint32), first_index,
+                                        snap_index)
+
+    def log_capacity(self, g):
+        return self.real.log_capacity(int(self.slot[g]))
+
     def load_timers(self, timers):
         t = self.real.get_timers()
         t[self.slot] = timers

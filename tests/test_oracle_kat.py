@@ -5,10 +5,13 @@ the oracle (oracle/raft_oracle.c).  The Go toolchain is absent from this image,
 so these tables ARE the oracle's pin (DESIGN.md "Parity").  Substitutions are
 named where a test drives a follower-side path the engine does not cover.
 """
+import ctypes as C
+
 import numpy as np
 import pytest
 
 from etcd_amd import abi
+from oracle import pyoracle
 from oracle.pyoracle import Inflights, Msg, Progress, Raft
 
 P, R, S = abi.HB_PR_PROBE, abi.HB_PR_REPLICATE, abi.HB_PR_SNAPSHOT
@@ -971,3 +974,91 @@ def test_rcommit_zero_before_first_step():
     r.r.log.committed = 3
     r.Step(Msg(APP, From=2, To=1, Term=2, LogTerm=1, Index=1, Commit=3))
     assert r.readMessages() == [] and r.Commit == 0
+
+
+# ---- the application's compaction (MemoryStorage.CreateSnapshot / Compact, raft/storage.go:172-214) ----
+@pytest.mark.parametrize("last, compact, wleft, wallow", [
+    (1000, [1001], [-1], False),                              # out of upper bound
+    (1000, [300, 500, 800, 900], [700, 500, 200, 100], True),
+    (1000, [300, 299], [700, -1], False),                     # out of lower bound
+])
+def test_compaction(last, compact, wleft, wallow):  # raft/log_test.go:490-536
+    r = Raft(1, [1], ents=[(i, 0) for i in range(1, last + 1)])
+    r.r.log.committed = last  # raftLog.maybeCommit(lastIndex, 0); appliedTo(committed)
+    allowed = True
+    for c, w in zip(compact, wleft):
+        rc = r.compact(c)
+        if rc != 0:  # the panic (recover) or the error: the row must not allow it
+            assert rc == (pyoracle.ERR_OUT_OF_BOUND if c > last else pyoracle.ERR_COMPACTED)
+            allowed = False
+            continue
+        assert len(r.entries()) == w  # len(raftLog.allEntries())
+        assert r.firstIndex == c + 1 and r.lastIndex == last
+    assert allowed == wallow
+
+
+def test_compaction_side_effects():  # raft/log_test.go:271-329
+    last = 1000
+    r = Raft(1, [1], ents=[(i, i) for i in range(1, last + 1)])  # (stable / unstable is the host's split)
+    r.r.log.committed = last  # maybeCommit(lastIndex, lastTerm)
+    offset = 500
+    assert r.compact(offset) == 0
+    assert r.lastIndex == last
+    log = C.byref(r.r.log)
+    for j in range(offset, last + 1):
+        assert r.term(j) == j
+        # matchTerm(j, j) (raft/log.go:239): maybeAppend with no entries matches
+        lastnew = C.c_uint64()
+        assert pyoracle.lib().orc_log_maybe_append(log, j, j, 0, None, 0, C.byref(lastnew)) == 1 and lastnew.value == j
+    assert r.term(offset - 1) == 0 and r.firstIndex == offset + 1  # below the dummy entry (raft/log.go:198-203)
+    prev = r.lastIndex
+    pyoracle.lib().orc_log_push(log, prev + 1, 1)  # raftLog.append(Entry{Index: last + 1, Term: last + 1})
+    assert r.lastIndex == prev + 1
+    assert r.entries()[-1:] == [(prev + 1, prev + 1)]  # entries(lastIndex, noLimit): one entry
+    assert r.r.log.nruns == r.lastIndex - offset + 1  # the trimmed log's runs: the dummy's and one per entry
+
+
+def test_compact_return_codes_and_snapshot():
+    """orc_raft_compact: CreateSnapshot(i) then Compact(i) (raft/storage.go:172-214).
+    The dummy entry keeps term(i); snap_index moves only when the snapshot is made;
+    ErrSnapOutOfDate leaves everything as it was; what the engine's log index knows stays."""
+    r = Raft(1, [1, 2], ents=[(1, 1), (2, 1), (3, 2), (4, 2), (5, 3), (6, 3)])
+    before = (r.r.sz_lo, r.r.tw_lo, r.r.tw_tfirst)
+    assert r.compact(3) == 0
+    assert (r.firstIndex, r.r.log.snap_index, r.term(3), r.term(2), r.term(4), r.term(5)) == (4, 0, 2, 0, 2, 3)
+    assert (r.r.log.runs[0].index, r.r.log.runs[0].term, r.r.log.nruns) == (3, 2, 2)
+    assert r.compact(3) == pyoracle.ERR_COMPACTED and r.compact(2, True) == pyoracle.ERR_COMPACTED
+    assert r.r.log.snap_index == 2  # CreateSnapshot(2) succeeded before Compact(2) answered ErrCompacted
+    assert r.compact(2, True) == pyoracle.ERR_SNAP_OUT_OF_DATE
+    assert r.compact(7, True) == pyoracle.ERR_OUT_OF_BOUND and r.compact(7) == pyoracle.ERR_OUT_OF_BOUND
+    assert (r.firstIndex, r.r.log.snap_index) == (4, 2)
+    assert r.compact(6, True) == 0  # at lastIndex: only the dummy entry is left
+    assert (r.firstIndex, r.lastIndex, r.r.log.snap_index, r.term(6), r.r.log.nruns, r.entries()) == (7, 6, 6, 3, 1, [])
+    assert (r.r.sz_lo, r.r.tw_lo, r.r.tw_tfirst) == before
+    g = r.to_group()
+    assert (g.first_index, g.last_index, g.snap_index) == (7, 6, 6)
+
+
+def test_provide_snap():  # raft/raft_test.go:1530-1560
+    """The reference reaches its compacted log by restore(snapshot{Index 11, Term 11});
+    here the same log (firstIndex 12, a snapshot at 11) is reached by compaction:
+    eleven entries of term 11, CreateSnapshot(11) + Compact(11)."""
+    sm = Raft(1, [1, 2], ents=[(i, 11) for i in range(1, 12)], hard=(11, 0, 11))
+    assert sm.compact(11, snapshot=True) == 0
+    assert (sm.firstIndex, sm.lastIndex, sm.r.log.snap_index, sm.term(11)) == (12, 11, 11, 11)
+    sm.becomeCandidate()
+    sm.becomeLeader()
+    sm.readMessages()
+    sm.pr(2).Next = sm.firstIndex  # node 2 needs a snapshot
+    sm.Step(Msg(APPRESP, From=2, To=1, Index=sm.pr(2).Next - 1, Reject=True))
+    msgs = sm.readMessages()
+    assert len(msgs) == 1 and msgs[0].Type == SNAP and msgs[0].snap_index == 11
+    assert (sm.pr(2).State, sm.pr(2).PendingSnapshot) == (S, 11)
+    # without the snapshot the reference panics "need non-empty snapshot" (raft/raft.go:252-254)
+    sm = Raft(1, [1, 2], ents=[(i, 11) for i in range(1, 12)], hard=(11, 0, 11))
+    assert sm.compact(11) == 0
+    sm.becomeCandidate()
+    sm.becomeLeader()
+    sm.pr(2).Next = sm.firstIndex
+    sm.Step(Msg(APPRESP, From=2, To=1, Index=sm.pr(2).Next - 1, Reject=True))
+    assert sm.fault == abi.HB_FAULT_EMPTY_SNAPSHOT
