@@ -1522,6 +1522,64 @@ __global__ void __launch_bounds__(ROUTE_THREADS) k_route(ApplyArgs a) {
 // FollowLane as far as it takes them (s_h / s_c: m.LogTerm, m.Commit).
 // STEADY (n = 3, two slots, not X mode): a wave whose lanes are all steady or
 // idle runs SteadyLane instead (a.steady; `nsteady` counts those waves).
+// The event words of a wave that took the steady path (evm: the lane's words,
+// 0 for an idle lane).  A lane's words are known, so there is one LDS add per
+// wave and chunk, the words of one kind side by side (a group's words keep
+// their order).
+__device__ __forceinline__ void steady_emit(const ApplyArgs& a, const SteadyLane& P, uint32_t evm, uint32_t lane,
+                                            uint64_t poff, uint64_t moff, uint32_t* l_pfill, uint32_t* l_fill) {
+  uint32_t tot = 0, base = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < SteadyLane::EW_P; ++j) tot += (uint32_t)__popcll(__ballot((evm >> j) & 1u));
+  if (tot && (lane & 63) == 0) base = atomicAdd(l_pfill, tot);
+  base = __builtin_amdgcn_readfirstlane(base);
+  uint64_t* chunk = a.ev + poff;
+#pragma unroll
+  for (uint32_t j = 0; j < SteadyLane::EW_P; ++j) {
+    const uint64_t m = __ballot((evm >> j) & 1u);
+    if ((evm >> j) & 1u) chunk[base + mbcnt64(m)] = P.word(j, lane);
+    base += (uint32_t)__popcll(m);
+  }
+  tot = 0;
+  base = 0;
+#pragma unroll
+  for (uint32_t j = SteadyLane::EW_P; j < SteadyLane::EW; ++j) tot += (uint32_t)__popcll(__ballot((evm >> j) & 1u));
+  if (tot && (lane & 63) == 0) base = atomicAdd(l_fill, tot);
+  base = __builtin_amdgcn_readfirstlane(base);
+  chunk = a.ev + moff;
+#pragma unroll
+  for (uint32_t j = SteadyLane::EW_P; j < SteadyLane::EW; ++j) {
+    const uint64_t m = __ballot((evm >> j) & 1u);
+    if ((evm >> j) & 1u) chunk[base + mbcnt64(m)] = P.word(j, lane);
+    base += (uint32_t)__popcll(m);
+  }
+}
+
+// What the fast lane decides from a group's meta word, message count and
+// dense proposal before it loads anything else (one definition for
+// k_apply_fast and both passes of k_route_fast: they must agree).
+//   live: the slot takes part (valid, n > 0, not faulted).
+//   leader: only a leader has fast-path work; any other live group is handed
+//     to k_apply whole, without loading its state here (resume bit 30:
+//     commit0 = its committed as k_apply loads it).
+//   nc: a group that has not stepped since an empty HardState (r.Commit = 0,
+//     M_NC) is the general lane's: its first Step sets r.Commit.
+//   lead: a leader whose state is loaded.  One the fast path cannot finish
+//     (more messages than slots) and without a dense proposal is handed over
+//     whole, its state unloaded (cfg4: every group; k_elect / k_apply load it).
+struct FastRole {
+  bool live, leader, nc, lead;
+};
+__device__ __forceinline__ FastRole fast_role(uint32_t mlo, bool valid, uint32_t cnt, uint32_t prop_raw,
+                                              uint32_t kmax) {
+  FastRole r;
+  r.live = valid && ((mlo >> 2) & 7) != 0 && ((mlo >> 17) & 0xF) == 0;
+  r.leader = r.live && (mlo & 3) == HB_STATE_LEADER;
+  r.nc = (mlo & (uint32_t)M_NC) != 0;
+  r.lead = r.leader && !r.nc && (cnt <= kmax || prop_raw != 0);
+  return r;
+}
+
 template <int NMAX, uint32_t KS, bool STEADY = false>
 __device__ __forceinline__ bool fast_step(const ApplyArgs& a, FollowLane<NMAX>& L, uint32_t part, uint32_t lane,
                                           bool live, bool lead, bool leader, bool fol, uint32_t prop_raw, uint32_t cnt,
@@ -1558,34 +1616,7 @@ __device__ __forceinline__ bool fast_step(const ApplyArgs& a, FollowLane<NMAX>& 
       if (lead && work) P.plan(L, prop_k, cnt, s_info, s_orig, s_term, s_index);
       const bool steady = lead && work && P.ok;
       if (__ballot(!(steady || idle)) == 0) {
-        // a lane's words are known: one LDS add per wave and chunk, the words
-        // of one kind side by side (a group's words keep their order)
-        const uint32_t evm = steady ? P.evm : 0u;
-        uint32_t tot = 0, base = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < SteadyLane::EW_P; ++j) tot += (uint32_t)__popcll(__ballot((evm >> j) & 1u));
-        if (tot && (lane & 63) == 0) base = atomicAdd(l_pfill, tot);
-        base = __builtin_amdgcn_readfirstlane(base);
-        uint64_t* chunk = a.ev + poff;
-#pragma unroll
-        for (uint32_t j = 0; j < SteadyLane::EW_P; ++j) {
-          const uint64_t m = __ballot((evm >> j) & 1u);
-          if ((evm >> j) & 1u) chunk[base + mbcnt64(m)] = P.word(j, lane);
-          base += (uint32_t)__popcll(m);
-        }
-        tot = 0;
-        base = 0;
-#pragma unroll
-        for (uint32_t j = SteadyLane::EW_P; j < SteadyLane::EW; ++j) tot += (uint32_t)__popcll(__ballot((evm >> j) & 1u));
-        if (tot && (lane & 63) == 0) base = atomicAdd(l_fill, tot);
-        base = __builtin_amdgcn_readfirstlane(base);
-        chunk = a.ev + moff;
-#pragma unroll
-        for (uint32_t j = SteadyLane::EW_P; j < SteadyLane::EW; ++j) {
-          const uint64_t m = __ballot((evm >> j) & 1u);
-          if ((evm >> j) & 1u) chunk[base + mbcnt64(m)] = P.word(j, lane);
-          base += (uint32_t)__popcll(m);
-        }
+        steady_emit(a, P, steady ? P.evm : 0u, lane, poff, moff, l_pfill, l_fill);
         if (steady) P.commit(L);
         // (no lane is flagged: resume, commit0, cnt and the slots are not
         // written, and the partition's hand-over bits stay 0)
@@ -1785,18 +1816,8 @@ __global__ void __launch_bounds__(PART, HB_FAST_WAVES) k_apply_fast(ApplyArgs a)
   // fewer for every leader; a group with no fast-path work wastes 52 bytes)
   if (gvalid) L.load_head();
   // A group takes part when its slot is live (n > 0) and not faulted.
-  const bool live = gvalid && L.n() != 0 && L.faulted() == 0;
-  // Only a leader has fast-path work: any other live group is handed to
-  // k_apply whole, without loading its state here (resume bit 30: commit0 =
-  // its committed as k_apply loads it).
-  const bool leader = live && L.state() == HB_STATE_LEADER;
-  // a group that has not stepped since an empty HardState (r.Commit = 0, M_NC)
-  // is the general lane's: its first Step sets r.Commit
-  const bool nc = (L.mlo & (uint32_t)M_NC) != 0;
-  // a leader the fast path cannot finish (more messages than slots) and
-  // without a dense proposal is handed over whole, its state unloaded (cfg4:
-  // every group; k_elect / k_apply load it)
-  const bool lead = leader && !nc && (cnt <= KMAX || prop_raw != 0);
+  const FastRole role = fast_role(L.mlo, gvalid, cnt, prop_raw, KMAX);
+  const bool live = role.live, leader = role.leader, nc = role.nc, lead = role.lead;
   // X mode: a follower whose messages all sit in its slots and that has no
   // dense proposal (stepFollower MsgProp forwards it: the general lane)
   const bool fol = X && live && !nc && L.state() == HB_STATE_FOLLOWER && cnt > 0 && cnt <= KMAX && prop_raw == 0;
@@ -1864,7 +1885,10 @@ __global__ void __launch_bounds__(PART, HB_FAST_WAVES) k_apply_fast(ApplyArgs a)
 // lanes (+6-9 %), 8 or 16 records in flight per lane in the route phase
 // (0 / +1.5 %), the slots staged as four 4-byte planes (neutral), the group
 // loop not unrolled (neutral), the next group's first-round loads issued
-// before this group's second round (+8 %: 128 VGPRs already, it spills).
+// before this group's second round in that one loop (+8 %: it spills).  With
+// two slots and not in X mode the lane's groups are stepped in two passes:
+// the steady group-waves by steady_pass, which has that look-ahead, then the
+// rest by the loop below.
 // ---------------------------------------------------------------------------
 #ifndef HB_RF_UNROLL
 #define HB_RF_UNROLL 4  // records in flight per lane in the route phase
@@ -1886,6 +1910,94 @@ template <uint32_t KMAX, bool X> struct RouteFastGeom {
   static constexpr uint32_t RG = 1u << RG_LOG;  // groups per workgroup
   static constexpr uint32_t NP = RG / PART;     // partitions per workgroup
 };
+// Group i of the workgroup (0 <= i < RG) as the fast lane names it.
+struct RouteFastGroup {
+  uint32_t p, part, lane, g;
+  bool valid;
+  __device__ __forceinline__ RouteFastGroup(const ApplyArgs& a, uint32_t part0, uint32_t i) {
+    // (a wave's 64 groups lie in one partition: kept as a scalar)
+    p = (uint32_t)__builtin_amdgcn_readfirstlane(i >> PART_LOG);
+    part = part0 + p;
+    lane = i & (PART - 1);
+    g = part * PART + lane;
+    valid = part < a.NB && g < a.S.G;
+  }
+};
+
+// Pass 1 of k_route_fast<2, false> over a lane's RG / RF_THREADS groups: the
+// group-waves whose lanes are all steady or idle are stepped here (what
+// fast_step's steady branch does, on SteadyIn instead of a FastLane), with the
+// next group's first round trip (SteadyHead) in flight under the current
+// group's second round trip, plan, events and stores.  H holds group 0's, issued
+// before the route phase.  A group-wave that is not steady is left untouched
+// (nothing is written before the vote) and its bit is set in the returned
+// mask; the wave owns its group-waves, so the mask is wave-uniform.  The
+// statistics a steady step can make non-zero are added to acc.
+template <uint32_t RG>
+__device__ __forceinline__ uint32_t steady_pass(const ApplyArgs& a, SteadyHead H, uint32_t part0,
+                                                const uint32_t* l_cnt, const uint4 (*l_slot)[RG],
+                                                const uint64_t* l_moff, uint32_t* l_pfill, uint32_t* l_fill,
+                                                uint32_t (&acc)[ST_N + 1], uint32_t& nsteady) {
+  constexpr uint32_t NW = RG / RF_THREADS;
+  uint32_t pend = 0;
+  uint32_t msgs = 0, commits = 0, entries = 0, nev = 0;
+  // (unrolled: the `k + 1 < NW` below must fold, or the loads under it sit
+  // behind a join like the one SteadyHead::load avoids)
+#pragma unroll
+  for (uint32_t k = 0; k < NW; ++k) {
+    const uint32_t i = threadIdx.x + k * RF_THREADS;
+    const RouteFastGroup R(a, part0, i);
+    SteadyIn L(a.S, R.g, H);
+    const uint32_t prop_k = H.props;  // (0 unless the group is valid)
+    const uint32_t c = R.valid ? l_cnt[i] : 0u;
+    const uint32_t cnt = c < CNT_MASK ? c : CNT_MASK;
+    const FastRole role = fast_role(L.mlo, R.valid, cnt, prop_k, 2);
+    const bool live = role.live, lead = role.lead;
+    if (lead) L.load_rest();
+    uint32_t s_info[2], s_orig[2];
+    uint64_t s_term[2], s_index[2];
+#pragma unroll
+    for (uint32_t j = 0; j < 2; ++j) {
+      const bool u = lead && cnt <= 2 && j < cnt;
+      slot_unpack(u ? l_slot[j][i] : make_uint4(0, 0, 0, 0), a.side, &s_info[j], &s_orig[j], &s_term[j], &s_index[j]);
+    }
+    uint64_t moff = l_moff[R.p];
+    moff = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)moff) |
+           (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(moff >> 32)) << 32;
+    // ---- the look-ahead: the next group's first round trip leaves now
+    if (k + 1 < NW) {  // (uniform)
+      const RouteFastGroup N(a, part0, i + RF_THREADS);
+      H.load(a.S, a.props, N.g, N.valid);
+    }
+    // ---- fast_step's steady branch
+    const bool work = live && (prop_k != 0 || cnt != 0);
+    const bool idle = !work && (!lead || (!(L.mlo & (uint32_t)M_RS) && L.self() < 3));
+    SteadyLane P;
+    P.ok = false;
+    P.evm = 0;
+    if (lead && work) P.plan(L, prop_k, cnt, s_info, s_orig, s_term, s_index);
+    const bool steady = lead && work && P.ok;
+    if (__ballot(!(steady || idle)) != 0) {
+      pend |= 1u << k;
+      continue;
+    }
+    const uint64_t poff = (uint64_t)R.part * PART * a.ev_per_msg;
+    if (R.lane == 0) a.ev_off[2 * R.part] = poff;
+    steady_emit(a, P, steady ? P.evm : 0u, R.lane, poff, moff, &l_pfill[R.p], &l_fill[R.p]);
+    if (steady) P.commit(L);
+    msgs += steady ? cnt : 0u;
+    commits += (uint32_t)(steady && P.committed != L.committed);
+    entries += steady ? (uint32_t)(P.last - L.last) : 0u;
+    nev += steady ? P.nev() : 0u;
+    if (a.steady_cnt && __ballot(R.g < a.S.G) != 0) ++nsteady;  // (tests; a wave of grid padding is not counted)
+  }
+  acc[ST_MSGS] += msgs;
+  acc[ST_COMMITS] += commits;
+  acc[ST_ENTRIES] += entries;
+  acc[ST_N] += nev;
+  return (uint32_t)__builtin_amdgcn_readfirstlane(pend);
+}
+
 template <uint32_t KMAX, bool X>
 __global__ void __launch_bounds__(RF_THREADS, HB_RF_WAVES) k_route_fast(ApplyArgs a) {
   constexpr int NMAX = 3;
@@ -1906,6 +2018,16 @@ __global__ void __launch_bounds__(RF_THREADS, HB_RF_WAVES) k_route_fast(ApplyArg
   const uint32_t tid = threadIdx.x;
   const uint32_t G = a.S.G;
   const uint32_t lg0 = w * RG;
+  const uint32_t part0 = (bk << sl) + w * NP;
+  constexpr bool STEADY = KMAX == 2 && !X;
+  // (pass 1, below: its first group's first round trip crosses the route phase in flight)
+  SteadyHead H0 = {};
+  if constexpr (STEADY) {
+    if (a.steady) {  // (uniform)
+      const RouteFastGroup R(a, part0, tid);
+      H0.load(a.S, a.props, R.g, R.valid);
+    }
+  }
   for (uint32_t i = tid; i < RG; i += RF_THREADS) l_cnt[i] = 0;
   if (tid < NP) {
     l_ptot[tid] = 0;
@@ -1958,7 +2080,6 @@ __global__ void __launch_bounds__(RF_THREADS, HB_RF_WAVES) k_route_fast(ApplyArg
     if ((tid & 63) == 0 && s) atomicAdd(&l_ptot[i >> PART_LOG], s);
   }
   __syncthreads();
-  const uint32_t part0 = (bk << sl) + w * NP;
   if (tid < NP) {
     const uint32_t part = part0 + tid;
     uint64_t mo = 0;
@@ -1975,9 +2096,18 @@ __global__ void __launch_bounds__(RF_THREADS, HB_RF_WAVES) k_route_fast(ApplyArg
   uint32_t acc[ST_N + 1];
 #pragma unroll
   for (int k = 0; k <= ST_N; ++k) acc[k] = 0;
-  constexpr bool STEADY = KMAX == 2 && !X;
   uint32_t nsteady = 0;
-  for (uint32_t i = tid; i < RG; i += RF_THREADS) {
+  // Two passes (two slots, not X mode): the steady group-waves first, on the
+  // lean lane with its look-ahead; then the others, as k_apply_fast steps
+  // them.  A lane's groups are distinct, so the order between them is free.
+  // (HB_FAST_STEADY=0: every group-wave is pass 2's.)
+  uint32_t pend = (1u << (RG / RF_THREADS)) - 1;
+  if constexpr (STEADY) {
+    if (a.steady)  // (uniform)
+      pend = steady_pass<RG>(a, H0, part0, l_cnt, l_slot, l_moff, l_pfill, l_fill, acc, nsteady);
+  }
+  for (uint32_t i = tid, kw = 0; i < RG; i += RF_THREADS, ++kw) {
+    if (STEADY && !((pend >> kw) & 1u)) continue;  // (uniform) stepped by pass 1
     // (a wave's 64 groups lie in one partition: with the steady path the
     // partition and its M chunk are kept as scalars, which frees the lane
     // registers the two paths need side by side)
@@ -1997,10 +2127,8 @@ __global__ void __launch_bounds__(RF_THREADS, HB_RF_WAVES) k_route_fast(ApplyArg
     const uint32_t c = gvalid ? l_cnt[i] : 0u;
     const uint32_t cnt = c < CNT_MASK ? c : CNT_MASK;
     if (gvalid) L.load_head();
-    const bool live = gvalid && L.n() != 0 && L.faulted() == 0;
-    const bool leader = live && L.state() == HB_STATE_LEADER;
-    const bool nc = (L.mlo & (uint32_t)M_NC) != 0;
-    const bool lead = leader && !nc && (cnt <= KMAX || prop_raw != 0);
+    const FastRole role = fast_role(L.mlo, gvalid, cnt, prop_raw, KMAX);
+    const bool live = role.live, leader = role.leader, nc = role.nc, lead = role.lead;
     const bool fol = X && live && !nc && L.state() == HB_STATE_FOLLOWER && cnt > 0 && cnt <= KMAX && prop_raw == 0;
     L.dirty = 0;
     L.nev = 0;
@@ -2027,9 +2155,10 @@ __global__ void __launch_bounds__(RF_THREADS, HB_RF_WAVES) k_route_fast(ApplyArg
       s_c[k] = (uint64_t)xe.z | ((uint64_t)xe.w << 32);
     }
     uint32_t vals[ST_N + 1];
-    const bool flagged = fast_step<NMAX, KMAX, STEADY>(a, L, part, lane, live, lead, leader, fol, prop_raw, cnt, s_info,
-                                                       s_orig, s_term, s_index, s_h, s_c, moff, &l_pfill[p],
-                                                       &l_fill[p], l_flag[p], nullptr, vals, nsteady);
+    // (the steady branch off: pass 1 has taken this group-wave's vote)
+    const bool flagged = fast_step<NMAX, KMAX, false>(a, L, part, lane, live, lead, leader, fol, prop_raw, cnt, s_info,
+                                                      s_orig, s_term, s_index, s_h, s_c, moff, &l_pfill[p],
+                                                      &l_fill[p], l_flag[p], nullptr, vals, nsteady);
     // (two slots, not X mode: only a leader's messages are stepped here and
     // each is a MsgAppResp, so that sum is the message sum: one register less)
 #pragma unroll

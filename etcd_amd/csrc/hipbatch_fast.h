@@ -582,8 +582,10 @@ struct SteadyLane {
     if (maybe_commit(term, first, EW_P + 2 * t)) bcast(W, first, EW_P + 2 * t + 1);
   }
 
-  // Steps the lane's proposal and its (at most two) messages on a copy of L.
-  __device__ __forceinline__ void plan(const FastLane<3>& L, uint32_t prop_k, uint32_t cnt,
+  // Steps the lane's proposal and its (at most two) messages on a copy of L
+  // (a FastLane<3>, or the lean SteadyIn below).
+  template <class LT>
+  __device__ __forceinline__ void plan(const LT& L, uint32_t prop_k, uint32_t cnt,
                                        const uint32_t (&s_info)[2], const uint32_t (&s_orig)[2],
                                        const uint64_t (&s_term)[2], const uint64_t (&s_index)[2]) {
     const uint32_t W = L.S.W;
@@ -660,7 +662,8 @@ struct SteadyLane {
   // every Next at last + 1): while it holds no Next is written; the one meta
   // store is for a group that gains it (or, a follower left behind without a
   // bcastAppend, loses it: then all three Next words are written).
-  __device__ __forceinline__ void commit(const FastLane<3>& L) const {
+  template <class LT>
+  __device__ __forceinline__ void commit(const LT& L) const {
     const DevState& S = L.S;
     const uint32_t g = L.g;
     const bool nx0 = (L.mlo & (uint32_t)M_NX) != 0;
@@ -684,6 +687,79 @@ struct SteadyLane {
     if (!nx && (touch_b || all)) at32(S.next, sb * S.G + g) = fb.next;
     if (fb.pm != pb0) at32(S.pm, sb * S.G + g) = fb.pm;
     if (add_b) *L.ring_at(sb, ring_b) = last;
+  }
+};
+
+// ---------------------------------------------------------------------------
+// The steady step's own view of a group (k_route_fast's pass 1):
+// only what SteadyLane::plan and commit read, so a loop over it carries none
+// of FastLane's heads, dirty bits, arrival or event sink.
+//
+// SteadyHead is the first round trip (what depends on nothing the lane reads):
+// 15 registers, loaded one group ahead.  The loads sit in straight-line code:
+// a lane without a valid group reads group 0's words (inside every array) and
+// drops them.  An exec-masked block would be a join in the control flow, and
+// at a join the wait-count pass assumes the shorter path, so the wait for the
+// current group's second round would become a wait for these loads too.  For
+// the same reason an absent props array is read as pm.
+// ---------------------------------------------------------------------------
+struct SteadyHead {
+  uint32_t mlo, props;
+  uint64_t term, committed, first, last, tfirst;
+  uint32_t pm[3];
+
+  __device__ __forceinline__ void load(const DevState& S, const uint32_t* props_in, uint32_t g, bool valid) {
+    const uint32_t gl = valid ? g : 0u;
+    const uint32_t* pr = props_in ? props_in : S.pm;  // (uniform select, no branch)
+    const uint32_t m = at32(reinterpret_cast<const uint32_t*>(S.meta), 2 * gl);  // little-endian low word
+    const uint32_t k = at32(pr, gl);
+    const uint64_t t = at32(S.term, gl), c = at32(S.commit, gl), f = at32(S.first, gl), l = at32(S.last, gl),
+                   tf = at32(S.tfirst, gl);
+    uint32_t p[3];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) p[s] = at32(S.pm, s * S.G + gl);
+    mlo = valid ? m : 0u;
+    props = (valid && props_in) ? k : 0u;
+    term = valid ? t : 0ull;
+    committed = valid ? c : 0ull;
+    first = valid ? f : 0ull;
+    last = valid ? l : 0ull;
+    tfirst = valid ? tf : 0ull;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) pm[s] = valid ? p[s] : 0u;
+  }
+};
+
+struct SteadyIn {
+  const DevState& S;
+  uint32_t g;
+  uint32_t mlo;
+  uint64_t term, committed, first, last, tfirst, tlast;
+  uint64_t match[3], next[3];
+  uint32_t pm[3];
+
+  __device__ __forceinline__ SteadyIn(const DevState& S_, uint32_t g_, const SteadyHead& H)
+      : S(S_), g(g_), mlo(H.mlo), term(H.term), committed(H.committed), first(H.first), last(H.last),
+        tfirst(H.tfirst), tlast(0), match{0, 0, 0}, next{0, 0, 0}, pm{H.pm[0], H.pm[1], H.pm[2]} {}
+  __device__ __forceinline__ uint32_t n() const { return (mlo >> 2) & 7; }
+  __device__ __forceinline__ uint32_t state() const { return mlo & 3; }
+  __device__ __forceinline__ uint32_t self() const { return (mlo >> 5) & 0xF; }
+  __device__ __forceinline__ uint32_t faulted() const { return (mlo >> 17) & 0xF; }
+  __device__ __forceinline__ uint64_t* ring_at(uint32_t s, uint32_t idx) const {
+    return S.ring + ((size_t)s * S.W + idx) * S.G + g;
+  }
+  // The second round trip: FastLane<3>::load_rest without the M_RS form (plan
+  // turns such a group down before it reads a Progress word) and without the
+  // ring heads (a steady ack frees its whole window unread).
+  __device__ __forceinline__ void load_rest() {
+    tlast = (mlo & (uint32_t)M_TL) ? last : at32(S.tlast, g);
+    const uint32_t sf = (mlo & (uint32_t)M_SM) ? self() : 0xFFu;
+    const bool nxl = (mlo & (uint32_t)M_NX) != 0;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+      match[s] = ((uint32_t)s == sf) ? last : at32(S.match, s * S.G + g);
+      next[s] = ((uint32_t)s == sf || nxl) ? last + 1 : at32(S.next, s * S.G + g);
+    }
   }
 };
 
