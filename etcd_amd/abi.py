@@ -113,6 +113,7 @@ HB_WIRE_ERROR = 3
 HB_WIRE_PANIC = 4
 HB_WIRE_BADGROUP = 5
 HB_DECODE_FOLLOW = 1      # hb_decode_caps bit: hb_decode_follow
+HB_ENCODE_ENTS = 1        # hb_encode_caps bit: hb_encode_ents
 
 HB_STAT_MSGS = 0
 HB_STAT_APPRESP = 1
@@ -248,6 +249,22 @@ class hb_out_batch(C.Structure):
         ("index", C.c_void_p),
         ("commit", C.c_void_p),
         ("hint", C.c_void_p),
+    ]
+
+
+class hb_ent_source(C.Structure):
+    """The entry windows of hb_encode_ents: a dense [capacity] window table over three per-entry
+    arrays and the payload bytes (device memory)."""
+    _fields_ = [
+        ("first", C.c_void_p),
+        ("count", C.c_void_p),
+        ("start", C.c_void_p),
+        ("n_ent", C.c_uint64),
+        ("eterm", C.c_void_p),
+        ("edesc", C.c_void_p),
+        ("edata", C.c_void_p),
+        ("data", C.c_void_p),
+        ("data_len", C.c_uint64),
     ]
 
 

@@ -4158,6 +4158,199 @@ __global__ void __launch_bounds__(ENC_SMALL_THREADS) k_enc_small(EncodeArgs a) {
   for (uint64_t i0 = 0; i0 < n; i0 += ENC_SMALL_THREADS) base += enc_tile(a, i0, n, base, write, l_win, sh16);
 }
 
+// hb_encode_ents: hb_encode with a covered MsgApp written whole, its entries
+// gathered from the caller's window table.  The same three passes, sizes and offsets 64-bit.
+// The write pass has two regimes, chosen per wave (uniformly): a wave whose 64 records span at
+// most ENCE_WIN - 16 bytes composes them in its LDS window, payload bytes included, and stores
+// the span as enc_tile does; a longer span is written in place, every lane its own prefix,
+// entry heads, payloads below ENCE_COOP bytes and suffix, and then the wave copies the
+// payloads of ENCE_COOP bytes and more together, record by record (wo_copy_lane).
+struct EnceArgs {
+  EncodeArgs e;  // bsum / bbase unused: the sums here are 64-bit
+  const uint32_t* group;
+  uint32_t capacity;
+  const uint64_t* first;
+  const uint32_t* count;
+  const uint64_t* start;
+  uint64_t n_ent;
+  const uint64_t* eterm;
+  const uint32_t* edesc;
+  const uint64_t* edata;
+  const uint8_t* data;
+  uint64_t data_len;
+  uint64_t* bsum;   // [blocks]
+  uint64_t* bbase;  // [blocks + 1]
+};
+// 64 records of 96 bytes: a wave of cfg2's MsgApps with one 16-byte entry (68 bytes each, about
+// 4.4 KB) fits, and so does any wave without a covered record (64 x WO_MAX).  4 waves x 6,160 B
+// = 24,640 B a workgroup: 6 workgroups in a CU's 160 KB.
+constexpr uint32_t ENCE_WIN = 64 * 96 + 16;
+constexpr uint32_t ENCE_COOP = 256;  // a payload this long is copied by the whole wave
+static_assert(ENCE_WIN % 16 == 0 && ENCE_WIN >= ENC_WIN, "read back as uint4; a payload-free wave always fits");
+static_assert(ENC_SMALL_THREADS / 64 * ENCE_WIN <= 64 * 1024, "k_ence_small's windows fit static LDS");
+
+struct EnceRec {
+  EncRec r;
+  bool cov;      // its entries are written here (else the split form, or no entries at all)
+  uint64_t pos;  // place of entry index + 1 in the per-entry arrays
+  uint64_t ne;   // entries carried
+};
+// record i, whether it is covered, and its encoded length
+__device__ __forceinline__ uint64_t ence_load(const EnceArgs& a, uint64_t i, uint64_t n, EnceRec* x) {
+  const uint32_t sz = enc_load(a.e, i, n, &x->r);
+  x->cov = false;
+  x->pos = x->ne = 0;
+  if (!x->r.ents) return sz;
+  const uint32_t g = a.group[i];
+  if (g >= a.capacity) return sz;
+  uint64_t run = 0;
+  if (!wo_ents_covered(x->r.index, a.e.hint[i], a.first[g], a.count[g], a.start[g], a.n_ent, a.eterm, a.edesc, a.edata,
+                       a.data_len, &x->pos, &x->ne, &run))
+    return sz;
+  x->cov = true;
+  x->r.ents = false;  // (status HB_WIRE_OK)
+  return sz + run;
+}
+// The record's bytes at dst: LDS in the short regime (coop = no limit: every payload is copied
+// here), global memory in the long one (payloads of `coop` bytes and more are left to the wave).
+// Returns whether a payload was left.
+__device__ __forceinline__ bool ence_put(const EnceArgs& a, const EnceRec& x, uint8_t* dst, uint32_t coop) {
+  const EncRec& r = x.r;
+  if (!x.cov) {
+    wo_write(dst, r.type, r.to, a.e.self_id, r.term, r.log_term, r.index, r.commit, r.reject, r.hint);
+    return false;
+  }
+  bool left = false;
+  dst += wo_write_prefix(dst, r.type, r.to, a.e.self_id, r.term, r.log_term, r.index);
+  for (uint64_t k = 0; k < x.ne; ++k) {
+    const uint32_t desc = a.edesc[x.pos + k];
+    dst += wo_entry_head(dst, desc, a.eterm[x.pos + k], r.index + 1 + k);
+    if (wo_desc_has_data(desc)) {
+      const uint32_t len = wo_desc_len(desc);
+      if (len >= coop) {
+        left = true;
+      } else {
+        const uint8_t* s = a.data + a.edata[x.pos + k];
+        for (uint32_t j = 0; j < len; ++j) dst[j] = s[j];
+      }
+      dst += len;
+    }
+  }
+  wo_write_suffix(dst, r.commit);
+  return left;
+}
+// One tile of blockDim.x records from i0, whose first byte is `base` (enc_tile's contract).
+__device__ __forceinline__ uint64_t ence_tile(const EnceArgs& a, uint64_t i0, uint64_t n, uint64_t base, bool write,
+                                              uint4* l_win, uint64_t* sh16) {
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t i = i0 + threadIdx.x;
+  EnceRec x;
+  const uint64_t sz = ence_load(a, i, n, &x);
+  uint64_t tot;
+  const uint64_t p = base + block_excl_scan64(sz, sh16, &tot);
+  if (i < n) {
+    a.e.off[i] = p;
+    uint8_t st = x.r.host ? (uint8_t)HB_WIRE_HOST : (uint8_t)HB_WIRE_OK;
+    if (x.r.ents)
+      st = (uint8_t)(HB_WIRE_SPLICE | wo_prefix_len(x.r.type, x.r.to, a.e.self_id, x.r.term, x.r.log_term, x.r.index));
+    a.e.status[i] = st;
+  }
+  if (!write) return tot;
+  const uint64_t lo = __shfl(p, 0), hi = __shfl(p + sz, 63);  // the wave's span
+  const bool fits = hi - lo <= ENCE_WIN - 16;  // short span: compose in LDS, store coalesced
+  uint4* wwin = l_win + (size_t)wave * (ENCE_WIN / 16);
+  uint8_t* win = reinterpret_cast<uint8_t*>(wwin);
+  const uintptr_t A = reinterpret_cast<uintptr_t>(a.e.bytes) + lo, B = reinterpret_cast<uintptr_t>(a.e.bytes) + hi;
+  const uintptr_t b16 = A & ~(uintptr_t)15;
+  if (fits) {
+    if (sz) (void)ence_put(a, x, win + (A - b16) + (p - lo), 0xFFFFFFFFu);
+  } else {  // long span: in place, then the long payloads by the whole wave
+    const bool left = sz ? ence_put(a, x, a.e.bytes + p, ENCE_COOP) : false;
+    uint64_t todo = __ballot(left);
+    while (todo) {
+      const int l = __ffsll((unsigned long long)todo) - 1;
+      todo &= todo - 1;
+      const uint64_t pos = __shfl(x.pos, l), ne = __shfl(x.ne, l), index = __shfl(x.r.index, l);
+      uint64_t cur = __shfl(p + wo_prefix_len(x.r.type, x.r.to, a.e.self_id, x.r.term, x.r.log_term, x.r.index), l);
+      for (uint64_t k = 0; k < ne; ++k) {  // (uniform: every lane walks record l's entries)
+        const uint32_t desc = a.edesc[pos + k];
+        cur += wo_entry_head_len(desc, a.eterm[pos + k], index + 1 + k);
+        if (wo_desc_has_data(desc)) {
+          const uint32_t len = wo_desc_len(desc);
+          if (len >= ENCE_COOP) wo_copy_lane(a.data + a.edata[pos + k], a.e.bytes + cur, len, lane, 64);
+          cur += len;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (fits && hi > lo) {
+    const uintptr_t A16 = (A + 15) & ~(uintptr_t)15, B16 = B & ~(uintptr_t)15;
+    if (A16 < B16) {
+      const uint32_t nc = (uint32_t)((B16 - A16) >> 4), c0 = (uint32_t)((A16 - b16) >> 4);
+      for (uint32_t c = lane; c < nc; c += 64) reinterpret_cast<uint4*>(A16)[c] = wwin[c0 + c];
+      for (uintptr_t y = A + lane; y < A16; y += 64) *reinterpret_cast<uint8_t*>(y) = win[y - b16];
+      for (uintptr_t y = B16 + lane; y < B; y += 64) *reinterpret_cast<uint8_t*>(y) = win[y - b16];
+    } else {
+      for (uintptr_t y = A + lane; y < B; y += 64) *reinterpret_cast<uint8_t*>(y) = win[y - b16];
+    }
+  }
+  __syncthreads();  // the windows are free for the next tile
+  return tot;
+}
+
+__global__ void __launch_bounds__(ENC_THREADS) k_ence_size(EnceArgs a) {
+  __shared__ uint64_t sh16[16];
+  EnceRec x;
+  const uint64_t sz = ence_load(a, (uint64_t)blockIdx.x * ENC_THREADS + threadIdx.x, enc_n(a.e), &x);
+  uint64_t tot;
+  (void)block_excl_scan64(sz, sh16, &tot);
+  if (threadIdx.x == 0) a.bsum[blockIdx.x] = tot;
+}
+__global__ void __launch_bounds__(1024) k_ence_scan(EnceArgs a, uint32_t nblk) {
+  __shared__ uint64_t sh16[16];
+  const uint32_t per = (nblk + 1023) / 1024, b0 = threadIdx.x * per;
+  uint64_t sum = 0;
+  for (uint32_t i = b0; i < b0 + per && i < nblk; ++i) sum += a.bsum[i];
+  uint64_t tot;
+  uint64_t run = block_excl_scan64(sum, sh16, &tot);
+  for (uint32_t i = b0; i < b0 + per && i < nblk; ++i) {
+    a.bbase[i] = run;
+    run += a.bsum[i];
+  }
+  if (threadIdx.x == 0) {
+    a.bbase[nblk] = tot;
+    a.e.off[enc_n(a.e)] = tot;
+    *a.e.total = tot;
+  }
+}
+__global__ void __launch_bounds__(ENC_THREADS) k_ence_write(EnceArgs a, uint32_t nblk) {
+  __shared__ uint64_t sh16[16];
+  __shared__ uint4 l_win[(ENC_THREADS / 64) * (ENCE_WIN / 16)];
+  const bool write = a.bbase[nblk] <= a.e.bytes_cap;  // else off, status and total only
+  (void)ence_tile(a, (uint64_t)blockIdx.x * ENC_THREADS, enc_n(a.e), a.bbase[blockIdx.x], write, l_win, sh16);
+}
+// A batch of at most ENC_SMALL_MAX records: all three in one workgroup.
+__global__ void __launch_bounds__(ENC_SMALL_THREADS) k_ence_small(EnceArgs a) {
+  __shared__ uint64_t sh16[16];
+  __shared__ uint4 l_win[(ENC_SMALL_THREADS / 64) * (ENCE_WIN / 16)];
+  const uint64_t n = enc_n(a.e);
+  uint64_t sum = 0;
+  for (uint64_t i = threadIdx.x; i < n; i += ENC_SMALL_THREADS) {
+    EnceRec x;
+    sum += ence_load(a, i, n, &x);
+  }
+  uint64_t tot;
+  (void)block_excl_scan64(sum, sh16, &tot);
+  if (threadIdx.x == 0) {
+    a.e.off[n] = tot;
+    *a.e.total = tot;
+  }
+  const bool write = tot <= a.e.bytes_cap;
+  uint64_t base = 0;
+  for (uint64_t i0 = 0; i0 < n; i0 += ENC_SMALL_THREADS) base += ence_tile(a, i0, n, base, write, l_win, sh16);
+}
+
 // hb_egress: the last step's event words -> an hb_out_batch.  One workgroup
 // per partition (its P chunk, then its M chunk), one lane per group.  The
 // words of a chunk interleave the partition's groups in emission order, and a
@@ -5126,6 +5319,8 @@ struct hb_handle {
   Dev<uint32_t> bin_hist;         // [256] bin totals, then [256][its tiles] tile histograms
   Dev<uint32_t> enc_sum;          // hb_encode: [blocks] bytes per pass-one workgroup
   Dev<uint64_t> enc_base;         // [blocks + 1]
+  Dev<uint64_t> ence_sum;         // hb_encode_ents: [blocks] bytes per pass-one workgroup
+  Dev<uint64_t> ence_base;        // [blocks + 1]
   Dev<uint64_t> rnd;              // the r.rand stream (hb_set_rand)
   // hb_move_groups scratch, reused (u64 words)
   Dev<uint64_t> mv_in;            // the call's slot lists and vacated slots' extents (one H2D copy)
@@ -6677,6 +6872,69 @@ int hb_encode(hb_handle* h, const hb_out_batch* in, uint64_t cap, const uint64_t
   hipLaunchKernelGGL(k_enc_size, dim3(nblk), dim3(ENC_THREADS), 0, h->stream, ea);
   hipLaunchKernelGGL(k_enc_scan, dim3(1), dim3(1024), 0, h->stream, ea, nblk);
   hipLaunchKernelGGL(k_enc_write, dim3(nblk), dim3(ENC_THREADS), 0, h->stream, ea, nblk);
+  return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
+}
+
+int hb_encode_caps(void) { return HB_ENCODE_ENTS; }
+
+int hb_encode_ents(hb_handle* h, const hb_out_batch* in, uint64_t cap, const uint64_t* n_dev, uint64_t self_id,
+                   const hb_ent_source* src, uint8_t* bytes, uint64_t bytes_cap, uint64_t* off, uint8_t* status,
+                   uint64_t* total) {
+  if (!h || !in || !src || !off || !status || !total || (bytes_cap && !bytes)) return HB_EINVAL;
+  if (!in->group || !in->info || !in->to || !in->term || !in->log_term || !in->index || !in->commit || !in->hint)
+    return HB_EINVAL;
+  if (!src->first || !src->count || !src->start) return HB_EINVAL;
+  if (src->n_ent && (!src->eterm || !src->edesc || !src->edata)) return HB_EINVAL;
+  if (src->data_len && !src->data) return HB_EINVAL;
+  const uint64_t cap_max = h->max_batch * (h->nmax + 4ull);
+  if (cap > cap_max || cap >= (1ull << 32)) return HB_EINVAL;
+  DeviceGuard guard(h->device);
+  EnceArgs ea;
+  ea.e.info = in->info;
+  ea.e.to = in->to;
+  ea.e.term = in->term;
+  ea.e.log_term = in->log_term;
+  ea.e.index = in->index;
+  ea.e.commit = in->commit;
+  ea.e.hint = in->hint;
+  ea.e.cap = cap;
+  ea.e.n_dev = dev_view(n_dev);
+  ea.e.self_id = self_id;
+  ea.e.bytes = bytes;
+  ea.e.bytes_cap = bytes_cap;
+  ea.e.off = off;
+  ea.e.status = status;
+  ea.e.total = dev_view(total);
+  ea.e.bsum = nullptr;
+  ea.e.bbase = nullptr;
+  ea.group = in->group;
+  ea.capacity = h->G;
+  ea.first = src->first;
+  ea.count = src->count;
+  ea.start = src->start;
+  ea.n_ent = src->n_ent;
+  ea.eterm = src->eterm;
+  ea.edesc = src->edesc;
+  ea.edata = src->edata;
+  ea.data = src->data;
+  ea.data_len = src->data_len;
+  ea.bsum = nullptr;
+  ea.bbase = nullptr;
+  const uint32_t nblk = (uint32_t)((cap + ENC_THREADS - 1) / ENC_THREADS);
+  if (nblk == 0 || (cap <= ENC_SMALL_MAX && !h->no_small)) {
+    hipLaunchKernelGGL(k_ence_small, dim3(1), dim3(ENC_SMALL_THREADS), 0, h->stream, ea);
+    return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
+  }
+  if (!h->ence_sum) {  // once, for the largest batch the handle takes
+    const uint64_t cm = cap_max >= (1ull << 32) ? (1ull << 32) - 1 : cap_max;
+    const uint64_t nb = (cm + ENC_THREADS - 1) / ENC_THREADS + 1;
+    if (const int rc = reserve_pair(h->ence_sum, nb, h->ence_base, nb + 1)) return rc;
+  }
+  ea.bsum = h->ence_sum.get();
+  ea.bbase = h->ence_base.get();
+  hipLaunchKernelGGL(k_ence_size, dim3(nblk), dim3(ENC_THREADS), 0, h->stream, ea);
+  hipLaunchKernelGGL(k_ence_scan, dim3(1), dim3(1024), 0, h->stream, ea, nblk);
+  hipLaunchKernelGGL(k_ence_write, dim3(nblk), dim3(ENC_THREADS), 0, h->stream, ea, nblk);
   return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
 }
 

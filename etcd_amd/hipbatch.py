@@ -130,6 +130,9 @@ def lib():
         "hb_egress": (C.c_int, [H, C.c_uint64, P(abi.hb_out_batch), C.c_uint64, C.c_void_p]),
         "hb_encode": (C.c_int, [H, P(abi.hb_out_batch), C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+        "hb_encode_caps": (C.c_int, []),
+        "hb_encode_ents": (C.c_int, [H, P(abi.hb_out_batch), C.c_uint64, C.c_void_p, C.c_uint64, P(abi.hb_ent_source),
+                                     C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
         "hb_set_egress_peers": (C.c_int, [H, C.c_void_p, C.c_uint32]),
         "hb_egress_bin": (C.c_int, [H, P(abi.hb_out_batch), C.c_uint64, C.c_void_p, P(abi.hb_out_batch), C.c_void_p,
                                     C.c_void_p]),
@@ -172,6 +175,26 @@ def _ptr(a):
     if hasattr(a, "data_ptr"):
         return a.data_ptr()
     return a.ctypes.data
+
+
+class EntSource:
+    """The entry source of Engine.encode_ents (hb_ent_source): keeps the device tensors alive
+    and builds the struct.  first / start u64 [capacity], count u32 [capacity]; eterm / edata
+    u64 and edesc u32 of one length (None for no entries); data u8 (None for no payload)."""
+
+    def __init__(self, first, count, start, eterm=None, edesc=None, edata=None, data=None, n_ent=None,
+                 data_len=None):
+        self.first, self.count, self.start = first, count, start
+        self.eterm, self.edesc, self.edata, self.data = eterm, edesc, edata, data
+        self.n_ent = (0 if edesc is None else len(edesc)) if n_ent is None else int(n_ent)
+        self.data_len = (0 if data is None else len(data)) if data_len is None else int(data_len)
+
+    def struct(self):
+        s = abi.hb_ent_source()
+        for name in ("first", "count", "start", "eterm", "edesc", "edata", "data"):
+            setattr(s, name, _ptr(getattr(self, name)))
+        s.n_ent, s.data_len = self.n_ent, self.data_len
+        return s
 
 
 class Engine:
@@ -426,6 +449,18 @@ class Engine:
         self._keep_enc = (batch, data, off, status, total, n_dev)
         _check("hb_encode", lib().hb_encode(self.h, C.byref(b), cap, _ptr(n_dev), self_id, _ptr(data),
                                             0 if data is None else len(data), _ptr(off), _ptr(status), _ptr(total)))
+
+    def encode_ents(self, self_id, batch, cap, src, data, off, status, total, n_dev=None):
+        """hb_encode_ents: encode() with the entries of every covered MsgApp written by the device
+        from `src` (an EntSource): such a record comes out whole with status HB_WIRE_OK; one
+        that `src` does not cover keeps HB_WIRE_SPLICE | prefix_len.  `data` must not overlap
+        the source's payload bytes."""
+        b = self._out_batch(batch)
+        s = src.struct()
+        self._keep_ence = (batch, src, data, off, status, total, n_dev)
+        _check("hb_encode_ents", lib().hb_encode_ents(self.h, C.byref(b), cap, _ptr(n_dev), self_id, C.byref(s),
+                                                      _ptr(data), 0 if data is None else len(data), _ptr(off),
+                                                      _ptr(status), _ptr(total)))
 
     def set_egress_peers(self, ids):
         """hb_set_egress_peers: the node table of egress_bin(); bin b is ids[b], bin len(ids)

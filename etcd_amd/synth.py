@@ -90,6 +90,23 @@ def cfg2_batch(groups, step, seed=0x5EED0002, xp=np):
     return dict(group=grp, info=info, term=term, index=index, hint=None, props=props)
 
 
+def cfg2_entry_source(groups, step=0, payload_len=16, etype=0):
+    """The entry source (hb_ent_source, numpy) of cfg2 step `step` from the groups as they were
+    before step 0: every group holds the one entry the step proposes, index last_index + step + 1
+    at the group's Term, Data = payload_len bytes that depend on the group and the position.
+    Entry of group g lies at position g, its payload at g * payload_len."""
+    G = len(groups)
+    gi = np.arange(G, dtype=np.uint64)
+    row = ((gi * np.uint64(131)) & np.uint64(0xFF)).astype(np.uint8)
+    col = ((np.arange(payload_len, dtype=np.uint64) * np.uint64(7) + np.uint64(step)) & np.uint64(0xFF)).astype(np.uint8)
+    data = (row[:, None] + col[None, :]).reshape(-1)  # (uint8: the sum wraps)
+    return dict(first=(groups["last_index"] + np.uint64(step + 1)).astype(np.uint64),
+                count=np.ones(G, dtype=np.uint32), start=gi.copy(),
+                eterm=groups["term"].astype(np.uint64),
+                edesc=np.full(G, A.hb_ent_desc(payload_len, etype, True), dtype=np.uint32),
+                edata=gi * np.uint64(payload_len), data=data)
+
+
 def global_ack_stream(G_total, n=3, seed=0x5EED0005):
     """The arrival stream of one cfg2/cfg5 step over a GLOBAL group-id space
     [0, G_total): every follower of every group acks once, in a random order

@@ -724,6 +724,59 @@ int  hb_encode(hb_handle* h, const hb_out_batch* in, uint64_t cap, const uint64_
                uint8_t* bytes, uint64_t bytes_cap, uint64_t* off /* [cap + 1] */, uint8_t* status /* [cap] */,
                uint64_t* total);
 
+/* hb_encode with the entries written by the device: a leader's MsgApp leaves as
+ * the whole message, no host splice.  Everything hb_encode says about n_dev,
+ * off, status, total and dense packing in record order holds; off[n] and *total
+ * = the byte count.  The entries come from a dense window table, one window per
+ * group (the three per-entry words are those hb_decode_follow writes): */
+#define HB_ENCODE_ENTS 1
+int  hb_encode_caps(void);            /* the encode features this library knows: HB_ENCODE_ENTS */
+typedef struct hb_ent_source {       /* every pointer is device memory */
+  const uint64_t* first;    /* [capacity] index of the first entry held for group g            */
+  const uint32_t* count;    /* [capacity] how many consecutive entries from first[g]; 0 = none */
+  const uint64_t* start;    /* [capacity] place of entry first[g] in the three per-entry arrays */
+  uint64_t        n_ent;    /* length of eterm / edesc / edata                                  */
+  const uint64_t* eterm;    /* Entry.Term                                                       */
+  const uint32_t* edesc;    /* HB_ENT_DESC(len(Data), Type, Data != nil)                        */
+  const uint64_t* edata;    /* offset in `data` of the first Data byte (ignored without Data)   */
+  const uint8_t*  data;
+  uint64_t        data_len;
+} hb_ent_source;
+/* Entry first[g] + j of group g lies at position start[g] + j of eterm / edesc /
+ * edata.  Windows may share positions and payload bytes.
+ * - A record without HB_OUT_ENTS, or an HB_WIRE_HOST record (HB_REF_OTHER,
+ *   HB_OUT_HOST), gets exactly the bytes and status hb_encode gives it.
+ * - A record with HB_OUT_ENTS and without HB_OUT_HOST, of group g =
+ *   in->group[i], carries entries (index, hint].  It is covered when
+ *     g < capacity, hint > index, count[g] > 0, index + 1 >= first[g],
+ *     (index + 1 - first[g]) + (hint - index) <= count[g],
+ *     start[g] + count[g] <= n_ent,
+ *     and for each of its entries with Data, edata + len <= data_len.
+ *   The rule is evaluated without wrap-around, and no element of a per-entry
+ *   array is read before the bounds that guard it have passed.
+ * - A covered record is written whole, status = HB_WIRE_OK: the prefix (fields
+ *   1-6), then per entry 0x3a, varint(Entry.Size()), 08 Type 10 varint(Term) 18
+ *   varint(Index) [22 varint(len) Data] with Index = index + 1 + k (what
+ *   Entry.MarshalTo writes, and the canonical shape hb_decode_follow accepts),
+ *   then the suffix (fields 8-11).
+ * - A record that is not covered is written as hb_encode writes it: prefix ||
+ *   suffix, status = HB_WIRE_SPLICE | prefix_len; the host completes that one.
+ *   Coverage is decided per record: covered and uncovered records mix freely.
+ * Sizes and offsets are 64-bit throughout: a record can be many megabytes and
+ * the total can pass 2^32; there is no cap x 91 bound.  When *total > bytes_cap
+ * no byte of `bytes` is written (off, status and total are): call again.
+ * Nothing outside data[0, data_len), the first n_ent elements of the per-entry
+ * arrays and bytes[0, total) is touched.  `bytes` must not overlap src->data.
+ * HB_EINVAL before any device work: a NULL handle, batch, batch array, src, off,
+ * status or total; bytes NULL with bytes_cap > 0; first, count or start NULL; a
+ * per-entry array NULL with n_ent > 0; data NULL with data_len > 0; cap >
+ * max_batch x (max_replicas + 4) or cap >= 2^32.  Asynchronous on the handle's
+ * stream; the struct itself is read during the call only. */
+int  hb_encode_ents(hb_handle* h, const hb_out_batch* in, uint64_t cap, const uint64_t* n_dev, uint64_t self_id,
+                    const hb_ent_source* src,
+                    uint8_t* bytes, uint64_t bytes_cap, uint64_t* off /* [cap + 1] */, uint8_t* status /* [cap] */,
+                    uint64_t* total);
+
 /* ---- per-peer egress -----------------------------------------------------
  * A transport has one stream per remote node: it needs one contiguous byte
  * span per destination, each group's messages still in r.msgs order inside
