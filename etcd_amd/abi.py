@@ -114,6 +114,13 @@ HB_WIRE_PANIC = 4
 HB_WIRE_BADGROUP = 5
 HB_DECODE_FOLLOW = 1      # hb_decode_caps bit: hb_decode_follow
 HB_ENCODE_ENTS = 1        # hb_encode_caps bit: hb_encode_ents
+HB_FRAME_V1 = 1           # hb_frame_caps bit: hb_frame / hb_unframe / hb_gid_dir_build
+# hb_unframe's fstatus
+HB_FRAME_OK = 0
+HB_FRAME_BAD_MAGIC = 1
+HB_FRAME_BAD_COUNT = 2
+HB_FRAME_BAD_ROUTE = 3
+HB_FRAME_BAD_LENGTH = 4
 
 HB_STAT_MSGS = 0
 HB_STAT_APPRESP = 1
@@ -265,6 +272,26 @@ class hb_ent_source(C.Structure):
         ("edata", C.c_void_p),
         ("data", C.c_void_p),
         ("data_len", C.c_uint64),
+    ]
+
+
+class hb_gid_dir(C.Structure):
+    """The group-id directory of hb_unframe: caller-owned device memory, key u64 [cap], slot u32 [cap]."""
+    _fields_ = [
+        ("key", C.c_void_p),
+        ("slot", C.c_void_p),
+        ("cap", C.c_uint64),
+    ]
+
+
+class hb_frame_in(C.Structure):
+    """One received frame of hb_unframe: where its index frame and its bytes lie, and who sent it."""
+    _fields_ = [
+        ("index_off", C.c_uint64),
+        ("index_len", C.c_uint64),
+        ("bytes_off", C.c_uint64),
+        ("bytes_len", C.c_uint64),
+        ("from_", C.c_uint64),
     ]
 
 

@@ -33,6 +33,7 @@
 #include "hipbatch_wire_in.h"
 #include "hipbatch_wire_out.h"
 #include "hipbatch_bin.h"
+#include "hipbatch_frame.h"
 
 using namespace hb;
 
@@ -5110,6 +5111,368 @@ __global__ void __launch_bounds__(BIN_SLOTS + 64) k_peer_spans(const uint64_t* o
 }
 
 // ============================================================================
+// framed peer streams (hb_gid_dir_build / hb_frame / hb_unframe)
+// ============================================================================
+constexpr uint32_t FRM_THREADS = 256;            // a tile: one row per lane
+constexpr uint32_t FRM_WORDS = BIN_SLOTS + 1;    // bin_off / ispan words (n_peers + 2 <= 257); frame bases
+constexpr uint32_t FRM_GRID_MAX = 2048;          // workgroups of a grid-stride launch: what 256 CUs hold at once
+static_assert(FRM_THREADS == BIN_SLOTS && FR_MAX_FRAMES == BIN_SLOTS, "a lane per bin and per frame");
+static_assert(ENC_SMALL_MAX % FRM_THREADS == 0 && ENC_SMALL_MAX / FRM_THREADS <= 64, "the small paths' tiles fit one wave's scan");
+
+// A launch's device counter to the caller's word (device or pinned memory), in
+// a launch of its own: a ticket in the counting launch would be one same-address
+// atomic per workgroup, and 16,384 of those take longer than the rows do.
+__global__ void k_count_out(const uint32_t* ctr, uint32_t* out32, uint64_t* out64) {
+  if (out32) *out32 = *ctr;
+  if (out64) *out64 = (uint64_t)*ctr;
+}
+
+// ---- the directory ---------------------------------------------------------------
+__global__ void __launch_bounds__(FRM_THREADS) k_gid_clear(uint64_t* key, uint64_t cap, uint32_t* ctr) {
+  for (uint64_t p = (uint64_t)blockIdx.x * FRM_THREADS + threadIdx.x; p < cap; p += (uint64_t)gridDim.x * FRM_THREADS)
+    key[p] = 0ull;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *ctr = 0u;
+}
+// gid[i] -> i for every non-zero id: the first probe that finds the key empty
+// claims it (a 64-bit compare-and-swap) and writes the slot; one that finds the
+// id itself is a duplicate and leaves the first claim.
+__global__ void __launch_bounds__(FRM_THREADS) k_gid_insert(const uint64_t* gid, uint32_t count, uint64_t* key,
+                                                            uint32_t* slot, uint64_t cap, uint32_t* ctr) {
+  const uint64_t mask = cap - 1;
+  for (uint64_t i = (uint64_t)blockIdx.x * FRM_THREADS + threadIdx.x; i < count;
+       i += (uint64_t)gridDim.x * FRM_THREADS) {
+    const uint64_t id = gid[i];
+    if (id == 0) continue;
+    uint64_t p = gd_mix(id) & mask;
+    for (uint64_t k = 0; k < cap; ++k) {
+      const uint64_t was = atomicCAS(reinterpret_cast<unsigned long long*>(key + p), 0ull, (unsigned long long)id);
+      if (was == 0) {
+        slot[p] = (uint32_t)i;
+        break;
+      }
+      if (was == id) {
+        atomicAdd(ctr, 1u);
+        break;
+      }
+      p = (p + 1) & mask;
+    }
+  }
+}
+
+// ---- hb_frame ----------------------------------------------------------------------
+struct FrameArgs {
+  const uint32_t* group;
+  const uint64_t* to;
+  const uint64_t* off;
+  const uint8_t* status;
+  const uint64_t* bin_off;  // [np + 2]
+  const uint64_t* span;     // [np + 2]
+  const uint64_t* gid;      // [capacity]
+  uint32_t capacity, np;
+  uint64_t max_rows;        // the handle's largest record batch: a larger bin_off is not believed
+  uint64_t self_id, seq;
+  uint8_t* index;
+  uint64_t index_cap;
+  uint64_t* ispan;          // [np + 2]
+  uint32_t* fstat;          // [np + 1]
+  uint32_t* cnt;            // tiled path: [BIN_SLOTS] holes per bin, then [BIN_SLOTS] oversize flags
+};
+// bin_off and the frames' places into LDS (all threads; ends on a barrier).
+// s_boff[b], b in [0, np + 1]; s_isp[b] = the bytes of the frames before bin b,
+// s_isp[np] = s_isp[np + 1] = the total.  A bin_off that does not ascend, or
+// ends past max_rows, is read as an empty batch: no row, no frame.
+__device__ __forceinline__ void frame_plan(const FrameArgs& a, uint64_t* s_boff, uint64_t* s_isp, uint64_t* sh16) {
+  const uint32_t t = threadIdx.x;
+  for (uint32_t b = t; b <= a.np + 1; b += FRM_THREADS) s_boff[b] = a.bin_off[b];
+  __syncthreads();
+  const bool bad = (t <= a.np && s_boff[t] > s_boff[t + 1]) || (t == 0 && s_boff[a.np + 1] > a.max_rows);
+  const bool any_bad = __syncthreads_or(bad) != 0;
+  if (any_bad)
+    for (uint32_t b = t; b <= a.np + 1; b += FRM_THREADS) s_boff[b] = 0;
+  __syncthreads();
+  uint64_t tot;
+  const uint64_t sz = t < a.np ? fr_isize(s_boff[t + 1] - s_boff[t]) : 0ull;
+  s_isp[t] = block_excl_scan64(sz, sh16, &tot);  // (t >= np: the total)
+  if (t == 0) s_isp[FRM_THREADS] = tot;
+  __syncthreads();
+}
+// Records [i0, i0 + FRM_THREADS) of the binned batch: a lane per record writes
+// its row's two words (rows of a bin are consecutive lanes: both stores coalesce)
+// and each wave adds its holes to cnt[bin] with one atomic per bin it touches.
+__device__ __forceinline__ void frame_tile(const FrameArgs& a, const uint64_t* s_boff, const uint64_t* s_isp,
+                                           uint64_t i0, uint64_t n, bool write, uint32_t* cnt) {
+  const uint64_t i = i0 + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63;
+  uint32_t b = 0;
+#pragma unroll
+  for (uint32_t step = 128; step >= 1; step >>= 1) {  // bins that end at or before i (bin_lookup's search)
+    const uint32_t m = b + step;
+    if (m <= a.np && s_boff[m] <= i) b = m;
+  }
+  const bool live = i < n && b < a.np;  // ("other" gets no frame)
+  bool hole = false, over = false;
+  if (live) {
+    const uint32_t g = a.group[i];
+    const bool ok = g < a.capacity;
+    const FrRow r = fr_row(a.status[i], ok, ok ? a.gid[g] : 0ull, a.off[i + 1] - a.off[i]);
+    hole = (r.len & FR_HOLE) != 0;
+    over = r.oversize;
+    if (write) {
+      const uint64_t c = s_boff[b + 1] - s_boff[b], j = i - s_boff[b];
+      uint8_t* f = a.index + s_isp[b];
+      *reinterpret_cast<uint64_t*>(f + fr_gid_at(j)) = r.gid;
+      *reinterpret_cast<uint32_t*>(f + fr_len_at(c, j)) = r.len;
+      if (j + 1 == c && (c & 1)) *reinterpret_cast<uint32_t*>(f + fr_len_at(c, c)) = 0u;
+    }
+  }
+  // the wave's runs of equal bins: the first lane of a run counts it
+  const uint32_t key = live ? b : 0xFFFFFFFFu;
+  const uint32_t prev = __shfl_up(key, 1);
+  const bool head = lane == 0 || prev != key;
+  const uint64_t hm = __ballot(hole), om = __ballot(over), sm = __ballot(head);
+  if (head && live) {
+    const uint64_t above = lane == 63 ? 0ull : (sm >> (lane + 1)) << (lane + 1);
+    const uint64_t upto = above ? (above & (0ull - above)) - 1 : ~0ull;  // lanes below the next run
+    const uint64_t run = upto & ~((1ull << lane) - 1);
+    const uint32_t nh = (uint32_t)__popcll(hm & run);
+    if (nh) atomicAdd(cnt + b, nh);
+    if (om & run) atomicOr(cnt + BIN_SLOTS + b, 1u);
+  }
+}
+// ispan, fstat and the headers: lane b is bin b (one workgroup, after every row).
+__device__ __forceinline__ void frame_heads(const FrameArgs& a, const uint64_t* s_boff, const uint64_t* s_isp,
+                                            bool write, const uint32_t* cnt) {
+  const uint32_t b = threadIdx.x;
+  if (b <= a.np + 1) a.ispan[b] = s_isp[b <= a.np ? b : a.np];
+  if (b + FRM_THREADS <= a.np + 1) a.ispan[b + FRM_THREADS] = s_isp[a.np];  // (np = 255: word 256)
+  if (b == a.np) a.fstat[b] = 0u;
+  if (b >= a.np) return;
+  const uint64_t c = s_boff[b + 1] - s_boff[b];
+  const bool over = cnt[BIN_SLOTS + b] != 0;
+  a.fstat[b] = over ? FR_OVERSIZE : cnt[b];
+  if (!write || c == 0) return;
+  FrHeader h;
+  h.magic = over ? 0u : FR_MAGIC;
+  h.flags = 0;
+  h.from = a.self_id;
+  h.to = a.to[s_boff[b]];  // (the bin holds the records whose `to` is ids[b])
+  h.seq = a.seq;
+  h.bytes = a.span[b + 1] - a.span[b];
+  h.count = (uint32_t)c;
+  h.holes = cnt[b];
+  fr_pack_header(a.index + s_isp[b], h);
+}
+__global__ void __launch_bounds__(FRM_THREADS) k_frame(FrameArgs a) {
+  __shared__ uint64_t s_boff[FRM_WORDS], s_isp[FRM_WORDS], sh16[16];
+  frame_plan(a, s_boff, s_isp, sh16);
+  const uint64_t n = s_boff[a.np + 1];
+  const bool write = s_isp[a.np] <= a.index_cap;
+  for (uint64_t i0 = (uint64_t)blockIdx.x * FRM_THREADS; i0 < n; i0 += (uint64_t)gridDim.x * FRM_THREADS)
+    frame_tile(a, s_boff, s_isp, i0, n, write, a.cnt);
+}
+__global__ void __launch_bounds__(FRM_THREADS) k_frame_heads(FrameArgs a) {
+  __shared__ uint64_t s_boff[FRM_WORDS], s_isp[FRM_WORDS], sh16[16];
+  frame_plan(a, s_boff, s_isp, sh16);
+  frame_heads(a, s_boff, s_isp, s_isp[a.np] <= a.index_cap, a.cnt);
+}
+// A handle whose largest record batch is at most ENC_SMALL_MAX: one workgroup, the counts in LDS.
+__global__ void __launch_bounds__(FRM_THREADS) k_frame_small(FrameArgs a) {
+  __shared__ uint64_t s_boff[FRM_WORDS], s_isp[FRM_WORDS], sh16[16];
+  __shared__ uint32_t s_cnt[2 * BIN_SLOTS];
+  s_cnt[threadIdx.x] = 0u;
+  s_cnt[threadIdx.x + BIN_SLOTS] = 0u;
+  frame_plan(a, s_boff, s_isp, sh16);
+  const uint64_t n = s_boff[a.np + 1];
+  const bool write = s_isp[a.np] <= a.index_cap;
+  for (uint64_t i0 = 0; i0 < n; i0 += FRM_THREADS) frame_tile(a, s_boff, s_isp, i0, n, write, s_cnt);
+  __syncthreads();
+  frame_heads(a, s_boff, s_isp, write, s_cnt);
+}
+
+// ---- hb_unframe --------------------------------------------------------------------
+// The frame table the host validated and copied: u64 words, FRM_WORDS bases
+// (base[k] = the first output row of frame k, base[nf] = n), then FR_MAX_FRAMES
+// words each of index_off, bytes_off, bytes_len and from.
+constexpr uint32_t UNF_IOFF = FRM_WORDS, UNF_BOFF = UNF_IOFF + FR_MAX_FRAMES, UNF_BLEN = UNF_BOFF + FR_MAX_FRAMES,
+                   UNF_FROM = UNF_BLEN + FR_MAX_FRAMES, UNF_WORDS = UNF_FROM + FR_MAX_FRAMES;
+struct UnfArgs {
+  const uint8_t* index;
+  const uint64_t* ft;  // [UNF_WORDS]
+  uint32_t nf;
+  uint64_t n, self_id;
+  const uint64_t* key;
+  const uint32_t* slot;
+  uint64_t cap;
+  uint64_t* off;
+  uint32_t* len;
+  uint32_t* group;
+  uint32_t* fstatus;    // [nf]
+  uint64_t* n_unknown;
+  uint64_t* tsum;       // tiled path: [tiles] bytes per tile
+  uint64_t* tbase;      // [tiles + 1] their scan
+  uint64_t* pbase;      // [nf + 1] bytes before each frame's first row
+  uint32_t* fst;        // [nf] fstatus for the write pass
+  uint32_t* ctr;        // [1] unknown rows
+};
+__device__ __forceinline__ void unf_tables(const UnfArgs& a, uint64_t* s_base, uint64_t* s_ioff) {
+  for (uint32_t k = threadIdx.x; k <= a.nf; k += blockDim.x) s_base[k] = a.ft[k];
+  for (uint32_t k = threadIdx.x; k < a.nf; k += blockDim.x) s_ioff[k] = a.ft[UNF_IOFF + k];
+  __syncthreads();
+}
+// The frame of output row r < n: the bases at or below r, less one (bin_lookup's search).
+__device__ __forceinline__ uint32_t unf_frame_of(const uint64_t* s_base, uint32_t nf, uint64_t r) {
+  uint32_t k = 0;
+#pragma unroll
+  for (uint32_t step = 128; step >= 1; step >>= 1) {
+    const uint32_t m = k + step;
+    if (m < nf && s_base[m] <= r) k = m;
+  }
+  return k;
+}
+// Row r's len word (the host checked the frame's extent against the buffer).
+__device__ __forceinline__ uint32_t unf_len_word(const UnfArgs& a, const uint64_t* s_base, const uint64_t* s_ioff,
+                                                 uint32_t k, uint64_t r) {
+  const uint64_t c = s_base[k + 1] - s_base[k];
+  return *reinterpret_cast<const uint32_t*>(a.index + s_ioff[k] + fr_len_at(c, r - s_base[k]));
+}
+__device__ __forceinline__ uint64_t unf_row_bytes(const UnfArgs& a, const uint64_t* s_base, const uint64_t* s_ioff,
+                                                  uint64_t r) {
+  return unf_len_word(a, s_base, s_ioff, unf_frame_of(s_base, a.nf, r), r) & FR_LEN_MASK;
+}
+// The bytes of tile t's rows (all threads; the value is the workgroup's).
+__device__ __forceinline__ uint64_t unf_tile_sum(const UnfArgs& a, const uint64_t* s_base, const uint64_t* s_ioff,
+                                                 uint64_t t, uint64_t* sh16) {
+  const uint64_t r = t * FRM_THREADS + threadIdx.x;
+  uint64_t tot;
+  (void)block_excl_scan64(r < a.n ? unf_row_bytes(a, s_base, s_ioff, r) : 0ull, sh16, &tot);
+  return tot;
+}
+// After the tiles' scan (tbase[0, nt], visible to the workgroup): the bytes
+// before every frame's first row, a wave per boundary, then a lane per frame
+// checks its header once.  All threads; ends on a barrier.
+__device__ __forceinline__ void unf_frames(const UnfArgs& a, const uint64_t* s_base, const uint64_t* s_ioff,
+                                           const uint64_t* tbase, uint64_t nt, uint64_t* s_pb, uint32_t* fst) {
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  for (uint32_t k = wave; k <= a.nf; k += nw) {
+    const uint64_t rb = s_base[k];
+    uint64_t p;
+    if (rb >= a.n) {
+      p = tbase[nt];
+    } else {
+      const uint64_t t = rb / FRM_THREADS;
+      uint64_t s = 0;
+      for (uint64_t r = t * FRM_THREADS + lane; r < rb; r += 64) s += unf_row_bytes(a, s_base, s_ioff, r);
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+      p = tbase[t] + s;
+    }
+    if (lane == 0) s_pb[k] = p;
+  }
+  __syncthreads();
+  for (uint32_t k = threadIdx.x; k < a.nf; k += blockDim.x) {
+    const uint64_t rows = s_base[k + 1] - s_base[k], blen = a.ft[UNF_BLEN + k];
+    uint32_t st;
+    if (rows == 0) st = blen == 0 ? FR_OK : FR_BAD_LENGTH;  // (no frame: no bytes)
+    else st = fr_validate(fr_parse_header(a.index + s_ioff[k]), rows, a.self_id, a.ft[UNF_FROM + k], blen,
+                          s_pb[k + 1] - s_pb[k]);
+    a.fstatus[k] = st;
+    fst[k] = st;
+  }
+  __syncthreads();
+}
+// Tile t, whose first row has `before` bytes of all frames in front of it: the
+// three output words of every row; cnt takes the rows of an unknown gid.
+__device__ __forceinline__ void unf_tile_write(const UnfArgs& a, const uint64_t* s_base, const uint64_t* s_ioff,
+                                               const uint64_t* s_pb, const uint32_t* fst, uint64_t t, uint64_t before,
+                                               uint64_t* sh16, uint32_t* cnt) {
+  const uint64_t r = t * FRM_THREADS + threadIdx.x;
+  const bool live = r < a.n;
+  uint32_t k = 0, w = 0;
+  if (live) {
+    k = unf_frame_of(s_base, a.nf, r);
+    w = unf_len_word(a, s_base, s_ioff, k, r);
+  }
+  uint64_t tot;
+  const uint64_t p = before + block_excl_scan64(live ? (uint64_t)(w & FR_LEN_MASK) : 0ull, sh16, &tot);
+  bool unknown = false;
+  if (live) {
+    uint64_t o = 0;
+    uint32_t l = 0, g = FR_NO_SLOT;
+    if (fst[k] == FR_OK) {
+      o = a.ft[UNF_BOFF + k] + (p - s_pb[k]);
+      const uint64_t id = *reinterpret_cast<const uint64_t*>(a.index + s_ioff[k] + fr_gid_at(r - s_base[k]));
+      if (!(w & FR_HOLE) && id != 0) {
+        g = gd_lookup(a.key, a.slot, a.cap, id);
+        unknown = g == FR_NO_SLOT;
+        if (!unknown) l = w & FR_LEN_MASK;
+      }
+    }
+    a.off[r] = o;
+    a.len[r] = l;
+    a.group[r] = g;
+  }
+  const uint64_t um = __ballot(unknown);
+  if ((threadIdx.x & 63) == 0 && um) atomicAdd(cnt, (uint32_t)__popcll(um));
+}
+__global__ void __launch_bounds__(FRM_THREADS) k_unf_sum(UnfArgs a) {
+  __shared__ uint64_t s_base[FRM_WORDS], s_ioff[FR_MAX_FRAMES], sh16[16];
+  unf_tables(a, s_base, s_ioff);
+  const uint64_t tot = unf_tile_sum(a, s_base, s_ioff, blockIdx.x, sh16);
+  if (threadIdx.x == 0) a.tsum[blockIdx.x] = tot;
+}
+__global__ void __launch_bounds__(1024) k_unf_scan(UnfArgs a, uint32_t nt) {
+  __shared__ uint64_t s_base[FRM_WORDS], s_ioff[FR_MAX_FRAMES], s_pb[FRM_WORDS], sh16[16];
+  unf_tables(a, s_base, s_ioff);
+  const uint32_t per = (nt + 1023) / 1024, t0 = threadIdx.x * per;
+  uint64_t sum = 0;
+  for (uint32_t i = t0; i < t0 + per && i < nt; ++i) sum += a.tsum[i];
+  uint64_t tot;
+  uint64_t run = block_excl_scan64(sum, sh16, &tot);
+  for (uint32_t i = t0; i < t0 + per && i < nt; ++i) {
+    a.tbase[i] = run;
+    run += a.tsum[i];
+  }
+  if (threadIdx.x == 0) {
+    a.tbase[nt] = tot;
+    a.ctr[0] = 0u;
+  }
+  __syncthreads();
+  unf_frames(a, s_base, s_ioff, a.tbase, nt, s_pb, a.fst);
+  for (uint32_t k = threadIdx.x; k <= a.nf; k += 1024) a.pbase[k] = s_pb[k];
+}
+__global__ void __launch_bounds__(FRM_THREADS) k_unf_write(UnfArgs a) {
+  __shared__ uint64_t s_base[FRM_WORDS], s_ioff[FR_MAX_FRAMES], s_pb[FRM_WORDS], sh16[16];
+  __shared__ uint32_t s_fst[FR_MAX_FRAMES];
+  unf_tables(a, s_base, s_ioff);
+  for (uint32_t k = threadIdx.x; k <= a.nf; k += FRM_THREADS) s_pb[k] = a.pbase[k];
+  for (uint32_t k = threadIdx.x; k < a.nf; k += FRM_THREADS) s_fst[k] = a.fst[k];
+  __syncthreads();
+  unf_tile_write(a, s_base, s_ioff, s_pb, s_fst, blockIdx.x, a.tbase[blockIdx.x], sh16, a.ctr);
+}
+// At most ENC_SMALL_MAX rows (at most 64 tiles): the three passes in one workgroup.
+__global__ void __launch_bounds__(FRM_THREADS) k_unf_small(UnfArgs a, uint32_t nt) {
+  __shared__ uint64_t s_base[FRM_WORDS], s_ioff[FR_MAX_FRAMES], s_pb[FRM_WORDS], sh16[16];
+  __shared__ uint64_t s_tsum[64], s_tbase[65];
+  __shared__ uint32_t s_fst[FR_MAX_FRAMES], s_cnt;
+  unf_tables(a, s_base, s_ioff);
+  if (threadIdx.x == 0) s_cnt = 0u;
+  for (uint32_t t = 0; t < nt; ++t) {
+    const uint64_t tot = unf_tile_sum(a, s_base, s_ioff, t, sh16);
+    if (threadIdx.x == 0) s_tsum[t] = tot;
+  }
+  __syncthreads();
+  uint64_t tot;
+  const uint64_t ex = block_excl_scan64(threadIdx.x < nt ? s_tsum[threadIdx.x] : 0ull, sh16, &tot);
+  if (threadIdx.x < nt) s_tbase[threadIdx.x] = ex;
+  if (threadIdx.x == 0) s_tbase[nt] = tot;
+  __syncthreads();
+  unf_frames(a, s_base, s_ioff, s_tbase, nt, s_pb, s_fst);
+  for (uint32_t t = 0; t < nt; ++t) unf_tile_write(a, s_base, s_ioff, s_pb, s_fst, t, s_tbase[t], sh16, &s_cnt);
+  __syncthreads();
+  if (threadIdx.x == 0) *a.n_unknown = (uint64_t)s_cnt;
+}
+
+// ============================================================================
 // host side
 // ============================================================================
 // Scratch that is allocated lazily or grown on demand is a DevBuf (hbmem.h):
@@ -5321,6 +5684,14 @@ struct hb_handle {
   Dev<uint64_t> enc_base;         // [blocks + 1]
   Dev<uint64_t> ence_sum;         // hb_encode_ents: [blocks] bytes per pass-one workgroup
   Dev<uint64_t> ence_base;        // [blocks + 1]
+  // framed peer streams (hb_frame / hb_unframe / hb_gid_dir_build): nothing of it exists before the first call
+  Dev<uint32_t> frm_cnt;          // hb_frame, tiled path: [256] holes per bin, [256] oversize flags
+  Dev<uint32_t> gd_ctr;           // hb_gid_dir_build: [1] duplicates
+  Pinned<uint64_t> unf_pin;       // hb_unframe: host image of the frame table (UNF_WORDS)
+  Dev<uint64_t> unf_ft;           // its device copy
+  hipEvent_t unf_done = nullptr;  // the last copy out of unf_pin has completed
+  Dev<uint64_t> unf_sum;          // [tiles] bytes per tile, [tiles + 1] their scan, [257] bytes before each frame
+  Dev<uint32_t> unf_st;           // [256] fstatus for the write pass, [1] unknown rows
   Dev<uint64_t> rnd;              // the r.rand stream (hb_set_rand)
   // hb_move_groups scratch, reused (u64 words)
   Dev<uint64_t> mv_in;            // the call's slot lists and vacated slots' extents (one H2D copy)
@@ -5772,6 +6143,7 @@ int hb_destroy(hb_handle* h) {
     if (ps.applied) (void)hipEventDestroy(ps.applied);
   }
   if (h->hstage_done) (void)hipEventDestroy(h->hstage_done);
+  if (h->unf_done) (void)hipEventDestroy(h->unf_done);
   if (h->in_ready) (void)hipEventDestroy(h->in_ready);
   if (h->prep) (void)hipStreamDestroy(h->prep);
   h->pool.release();
@@ -7030,6 +7402,145 @@ int hb_peer_spans(hb_handle* h, const uint64_t* off, const uint64_t* bin_off, ui
   DeviceGuard guard(h->device);
   hipLaunchKernelGGL(k_peer_spans, dim3(1), dim3(BIN_SLOTS + 64), 0, h->stream, off, dev_view(bin_off), dev_view(span),
                      h->bin_np);
+  return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
+}
+
+// ---- framed peer streams ---------------------------------------------------------
+int hb_frame_caps(void) { return HB_FRAME_V1; }
+uint64_t hb_frame_size(uint64_t rows) { return rows > FR_MAX_ROWS ? UINT64_MAX : fr_isize(rows); }
+uint64_t hb_frame_rows(uint64_t index_len) { return fr_rows(index_len); }
+
+int hb_gid_dir_build(hb_handle* h, const uint64_t* gid, uint32_t count, uint64_t* key, uint32_t* slot, uint64_t cap,
+                     uint32_t* dups) {
+  if (!h || !key || !slot || !dups || (count && !gid)) return HB_EINVAL;
+  if (!gd_cap_ok(cap, count)) return HB_EINVAL;
+  DeviceGuard guard(h->device);
+  hipStream_t ds = h->in_stream_set ? h->in_stream : h->stream;  // as hb_decode
+  if (const int rc = h->gd_ctr.reserve(1)) return rc;
+  const uint64_t cb = (cap + FRM_THREADS - 1) / FRM_THREADS, ib = ((uint64_t)count + FRM_THREADS - 1) / FRM_THREADS;
+  hipLaunchKernelGGL(k_gid_clear, dim3((unsigned)std::min<uint64_t>(cb, FRM_GRID_MAX)), dim3(FRM_THREADS), 0, ds, key,
+                     cap, h->gd_ctr.get());
+  hipLaunchKernelGGL(k_gid_insert, dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>(ib, 1), FRM_GRID_MAX)),
+                     dim3(FRM_THREADS), 0, ds, gid, count, key, slot, cap, h->gd_ctr.get());
+  hipLaunchKernelGGL(k_count_out, dim3(1), dim3(1), 0, ds, h->gd_ctr.get(), dev_view(dups), (uint64_t*)nullptr);
+  return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
+}
+
+int hb_frame(hb_handle* h, const hb_out_batch* binned, const uint64_t* off, const uint8_t* status,
+             const uint64_t* bin_off, const uint64_t* span, const uint64_t* gid, uint64_t self_id, uint64_t seq,
+             uint8_t* index, uint64_t index_cap, uint64_t* ispan, uint32_t* fstat) {
+  if (!h || !binned || !off || !status || !bin_off || !span || !gid || !ispan || !fstat) return HB_EINVAL;
+  if (!binned->group || !binned->to || (index_cap && !index)) return HB_EINVAL;
+  if (reinterpret_cast<uintptr_t>(index) % 8) return HB_EINVAL;  // the columns are stored as words
+  if (!h->bin_table) return HB_EINVAL;
+  DeviceGuard guard(h->device);
+  FrameArgs a;
+  a.group = binned->group;
+  a.to = binned->to;
+  a.off = off;
+  a.status = status;
+  a.bin_off = dev_view(bin_off);
+  a.span = dev_view(span);
+  a.gid = gid;
+  a.capacity = h->G;
+  a.np = h->bin_np;
+  a.max_rows = std::min<uint64_t>(h->max_batch * (h->nmax + 4ull), (1ull << 32) - 1);  // hb_egress_bin's bound
+  a.self_id = self_id;
+  a.seq = seq;
+  a.index = index;
+  a.index_cap = index_cap;
+  a.ispan = dev_view(ispan);
+  a.fstat = dev_view(fstat);
+  a.cnt = nullptr;
+  // the batch's size is bin_off's last word, on the device: the small-step rule goes by the handle's bound
+  if (a.max_rows <= ENC_SMALL_MAX && !h->no_small) {
+    hipLaunchKernelGGL(k_frame_small, dim3(1), dim3(FRM_THREADS), 0, h->stream, a);
+    return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
+  }
+  if (const int rc = h->frm_cnt.reserve(2 * BIN_SLOTS)) return rc;
+  a.cnt = h->frm_cnt.get();
+  HB_CHECK(hipMemsetAsync(a.cnt, 0, 2 * BIN_SLOTS * sizeof(uint32_t), h->stream));
+  const uint64_t nb = (a.max_rows + FRM_THREADS - 1) / FRM_THREADS;
+  hipLaunchKernelGGL(k_frame, dim3((unsigned)std::min<uint64_t>(std::max<uint64_t>(nb, 1), FRM_GRID_MAX)),
+                     dim3(FRM_THREADS), 0, h->stream, a);
+  hipLaunchKernelGGL(k_frame_heads, dim3(1), dim3(FRM_THREADS), 0, h->stream, a);
+  return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
+}
+
+int hb_unframe(hb_handle* h, const uint8_t* index, uint64_t index_size, const hb_frame_in* frames, uint32_t n_frames,
+               uint64_t self_id, const hb_gid_dir* dir, uint64_t bytes_size, uint64_t* off, uint32_t* len,
+               uint32_t* group, uint64_t n, uint32_t* fstatus, uint64_t* n_unknown) {
+  if (!h || !dir || !n_unknown || (n_frames && (!frames || !fstatus))) return HB_EINVAL;
+  if (!dir->key || !dir->slot || dir->cap == 0 || (dir->cap & (dir->cap - 1))) return HB_EINVAL;
+  if (n && (!index || !off || !len || !group)) return HB_EINVAL;
+  if (n_frames > FR_MAX_FRAMES || n > h->max_batch) return HB_EINVAL;
+  if (reinterpret_cast<uintptr_t>(index) % 8) return HB_EINVAL;
+  uint64_t base[FRM_WORDS];
+  uint64_t rows_all = 0;
+  for (uint32_t k = 0; k < n_frames; ++k) {
+    const hb_frame_in& f = frames[k];
+    if (f.index_off % 8) return HB_EINVAL;
+    if (f.index_off > index_size || f.index_len > index_size - f.index_off) return HB_EINVAL;
+    if (f.bytes_off > bytes_size || f.bytes_len > bytes_size - f.bytes_off) return HB_EINVAL;
+    const uint64_t rows = fr_rows(f.index_len);
+    if (rows == FR_IMPOSSIBLE) return HB_EINVAL;
+    base[k] = rows_all;
+    rows_all += rows;  // (at most 256 x 2^32)
+  }
+  base[n_frames] = rows_all;
+  if (rows_all != n) return HB_EINVAL;
+  DeviceGuard guard(h->device);
+  hipStream_t ds = h->in_stream_set ? h->in_stream : h->stream;  // as hb_decode
+  if (!h->unf_ft) {  // once, for the largest batch the handle takes
+    const uint64_t nt = (h->max_batch + FRM_THREADS - 1) / FRM_THREADS;
+    if (h->unf_pin.reserve(UNF_WORDS) != HB_OK || h->unf_sum.reserve(2 * nt + 1 + FRM_WORDS) != HB_OK ||
+        h->unf_st.reserve(FR_MAX_FRAMES + 1) != HB_OK || h->unf_ft.reserve(UNF_WORDS) != HB_OK ||
+        (!h->unf_done && hipEventCreateWithFlags(&h->unf_done, hipEventDisableTiming) != hipSuccess)) {
+      h->unf_ft.release();
+      return HB_ENOMEM;
+    }
+  }
+  HB_CHECK(hipEventSynchronize(h->unf_done));  // the previous call's copy has left the block
+  uint64_t* ft = h->unf_pin.get();
+  std::memset(ft, 0, UNF_WORDS * sizeof(uint64_t));
+  for (uint32_t k = 0; k <= n_frames; ++k) ft[k] = base[k];
+  for (uint32_t k = 0; k < n_frames; ++k) {
+    ft[UNF_IOFF + k] = frames[k].index_off;
+    ft[UNF_BOFF + k] = frames[k].bytes_off;
+    ft[UNF_BLEN + k] = frames[k].bytes_len;
+    ft[UNF_FROM + k] = frames[k].from;
+  }
+  HB_CHECK(hipMemcpyAsync(h->unf_ft.get(), ft, UNF_WORDS * sizeof(uint64_t), hipMemcpyHostToDevice, ds));
+  HB_CHECK(hipEventRecord(h->unf_done, ds));
+  const uint64_t nt_max = (h->max_batch + FRM_THREADS - 1) / FRM_THREADS;
+  UnfArgs a;
+  a.index = index;
+  a.ft = h->unf_ft.get();
+  a.nf = n_frames;
+  a.n = n;
+  a.self_id = self_id;
+  a.key = dir->key;
+  a.slot = dir->slot;
+  a.cap = dir->cap;
+  a.off = off;
+  a.len = len;
+  a.group = group;
+  a.fstatus = dev_view(fstatus);
+  a.n_unknown = dev_view(n_unknown);
+  a.tsum = h->unf_sum.get();
+  a.tbase = a.tsum + nt_max;
+  a.pbase = a.tbase + nt_max + 1;
+  a.fst = h->unf_st.get();
+  a.ctr = a.fst + FR_MAX_FRAMES;
+  const uint32_t nt = (uint32_t)((n + FRM_THREADS - 1) / FRM_THREADS);
+  if (n <= ENC_SMALL_MAX && !h->no_small) {
+    hipLaunchKernelGGL(k_unf_small, dim3(1), dim3(FRM_THREADS), 0, ds, a, nt);
+    return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
+  }
+  if (nt) hipLaunchKernelGGL(k_unf_sum, dim3(nt), dim3(FRM_THREADS), 0, ds, a);
+  hipLaunchKernelGGL(k_unf_scan, dim3(1), dim3(1024), 0, ds, a, nt);
+  if (nt) hipLaunchKernelGGL(k_unf_write, dim3(nt), dim3(FRM_THREADS), 0, ds, a);
+  hipLaunchKernelGGL(k_count_out, dim3(1), dim3(1), 0, ds, a.ctr, (uint32_t*)nullptr, a.n_unknown);
   return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
 }
 

@@ -137,6 +137,15 @@ def lib():
         "hb_egress_bin": (C.c_int, [H, P(abi.hb_out_batch), C.c_uint64, C.c_void_p, P(abi.hb_out_batch), C.c_void_p,
                                     C.c_void_p]),
         "hb_peer_spans": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "hb_frame_caps": (C.c_int, []),
+        "hb_frame_size": (C.c_uint64, [C.c_uint64]),
+        "hb_frame_rows": (C.c_uint64, [C.c_uint64]),
+        "hb_gid_dir_build": (C.c_int, [H, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+        "hb_frame": (C.c_int, [H, P(abi.hb_out_batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+        "hb_unframe": (C.c_int, [H, C.c_void_p, C.c_uint64, P(abi.hb_frame_in), C.c_uint32, C.c_uint64,
+                                 P(abi.hb_gid_dir), C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                 C.c_void_p, C.c_void_p]),
         "hb_events_device": (C.c_int, [H, P(C.c_void_p), P(C.c_void_p), P(C.c_void_p), P(C.c_uint32)]),
         "hb_copy_events": (C.c_int, [H, C.c_void_p, C.c_uint64, P(C.c_uint64)]),
         "hb_events_to_host": (C.c_int, [H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
@@ -195,6 +204,21 @@ class EntSource:
             setattr(s, name, _ptr(getattr(self, name)))
         s.n_ent, s.data_len = self.n_ent, self.data_len
         return s
+
+
+class GidDir:
+    """The group-id directory of Engine.unframe (hb_gid_dir): keeps the device tensors alive and
+    builds the struct.  key u64 [cap], slot u32 [cap]; cap a power of two, at least 64 and at
+    least twice the ids it holds."""
+
+    def __init__(self, key, slot, cap=None):
+        self.key, self.slot = key, slot
+        self.cap = len(key) if cap is None else int(cap)
+
+    def struct(self):
+        d = abi.hb_gid_dir()
+        d.key, d.slot, d.cap = _ptr(self.key), _ptr(self.slot), self.cap
+        return d
 
 
 class Engine:
@@ -483,6 +507,40 @@ class Engine:
         from an encode() of the binned batch, peer b's bytes are data[span[b]:span[b + 1]]."""
         self._keep_span = (off, bin_off, span)
         _check("hb_peer_spans", lib().hb_peer_spans(self.h, _ptr(off), _ptr(bin_off), _ptr(span)))
+
+    # ---- framed peer streams -----------------------------------------------------
+    def gid_dir_build(self, gid, dir, dups, count=None):
+        """hb_gid_dir_build: `dir` (a GidDir) cleared, then gid[i] -> i for every non-zero id of the
+        device u64 tensor `gid`; dups = a device (or pinned) u32 that takes the repeated ids."""
+        self._keep_gd = (gid, dir, dups)
+        _check("hb_gid_dir_build", lib().hb_gid_dir_build(self.h, _ptr(gid), len(gid) if count is None else count,
+                                                          _ptr(dir.key), _ptr(dir.slot), dir.cap, _ptr(dups)))
+
+    def frame(self, self_id, seq, binned, off, status, bin_off, span, gid, index, ispan, fstat, index_cap=None):
+        """hb_frame: the index frames of a binned batch (egress_bin's out and bin_off, encode's off and
+        status of it, peer_spans' span; gid = device u64 [capacity], the id of every slot) into the
+        device u8 tensor `index`; ispan u64 [peers + 2] and fstat u32 [peers + 1], device or pinned."""
+        b = self._out_batch(binned)
+        self._keep_fr = (binned, off, status, bin_off, span, gid, index, ispan, fstat)
+        cap = (0 if index is None else len(index)) if index_cap is None else index_cap
+        _check("hb_frame", lib().hb_frame(self.h, C.byref(b), _ptr(off), _ptr(status), _ptr(bin_off), _ptr(span),
+                                          _ptr(gid), self_id, seq, _ptr(index), cap, _ptr(ispan), _ptr(fstat)))
+
+    def unframe(self, self_id, index, frames, dir, bytes_size, off, length, group, fstatus, n_unknown, n=None,
+                index_size=None):
+        """hb_unframe: received frames -> decode_follow's off / length / group (device tensors of n
+        rows).  frames = [(index_off, index_len, bytes_off, bytes_len, from), ...] in the order their
+        rows take; dir = a GidDir; fstatus u32 [len(frames)] and n_unknown u64, device or pinned."""
+        fr = (abi.hb_frame_in * max(len(frames), 1))()
+        for k, f in enumerate(frames):
+            fr[k].index_off, fr[k].index_len, fr[k].bytes_off, fr[k].bytes_len, fr[k].from_ = (int(v) for v in f)
+        d = dir.struct()
+        self._keep_unf = (index, dir, off, length, group, fstatus, n_unknown)
+        isz = (0 if index is None else len(index)) if index_size is None else index_size
+        _check("hb_unframe", lib().hb_unframe(self.h, _ptr(index), isz, fr, len(frames), self_id, C.byref(d),
+                                              bytes_size, _ptr(off), _ptr(length), _ptr(group),
+                                              (0 if off is None else len(off)) if n is None else n, _ptr(fstatus),
+                                              _ptr(n_unknown)))
 
     def step_batch(self, batch, **kw):
         return self.step(batch["group"], batch["info"], batch["term"], batch["index"],

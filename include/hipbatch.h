@@ -816,6 +816,119 @@ int  hb_egress_bin(hb_handle* h, const hb_out_batch* in, uint64_t cap, const uin
  * pinned memory.  HB_EINVAL: a NULL argument, no table set. */
 int  hb_peer_spans(hb_handle* h, const uint64_t* off, const uint64_t* bin_off, uint64_t* span);
 
+/* ---- framed peer streams -------------------------------------------------
+ * A peer's byte span is a run of raftpb.Message records: it holds neither
+ * their boundaries nor their groups (a Message carries no group id,
+ * raft/multinode.go:432-439), and group[i] of a record batch is the sender's
+ * slot, which means nothing on another node.  What two nodes share is the
+ * 64-bit MultiNode group id.  hb_frame writes one index frame per non-empty
+ * peer bin beside the bytes: the group id and the length of every record, so a
+ * transport ships two spans per peer (index[ispan[b], ispan[b+1]) and
+ * bytes[span[b], span[b+1])) and nothing per record.  hb_unframe turns the
+ * frames of several peers into the off / len / group arrays hb_decode_follow
+ * takes, through a device directory from group id to the receiver's slot; no
+ * host read lies between.  An addition inside ABI 8: a library that lacks
+ * hb_frame_caps lacks all of it.
+ *
+ * The index frame, little-endian, every frame at a multiple of 8 bytes:
+ *    0 u32 magic 0x31464248 ("HBF1")    4 u32 flags  0
+ *    8 u64 from  the sender's node id  16 u64 to     the destination's (ids[b])
+ *   24 u64 seq   the caller's number   32 u64 bytes  span[b+1] - span[b]
+ *   40 u32 count rows c                44 u32 holes  rows with the hole bit
+ *   48 u64 gid[c]
+ *   48 + 8c  u32 len[c]   bits 0..30 the record's byte length, bit 31 = hole
+ *            (4 zero bytes when c is odd)
+ * hb_frame_size(c) = 48 + 12c + 4(c & 1) for c > 0 and 0 for c = 0 (an empty
+ * bin makes no frame; UINT64_MAX for c >= 2^32); it is injective, and
+ * hb_frame_rows is its inverse (UINT64_MAX for a length no count gives): a
+ * receiver takes c from the frame's length.  Row j is the bin's j-th record;
+ * the records' bytes are the peer's span as it is.  A hole is a row whose
+ * bytes, if any, lie in the span but are no message for the receiver: status[i]
+ * != HB_WIRE_OK (HB_WIRE_HOST with length 0, or HB_WIRE_SPLICE | k: a split
+ * MsgApp must not be decoded as one without entries), group[i] >= capacity (its
+ * gid word is 0), or a group whose id is 0 (unset). */
+#define HB_FRAME_V1 1
+int  hb_frame_caps(void);                       /* the frame features this library knows: HB_FRAME_V1 */
+uint64_t hb_frame_size(uint64_t rows);
+uint64_t hb_frame_rows(uint64_t index_len);
+
+/* The directory, group id -> slot: open addressing over cap keys (a power of
+ * two), first probe splitmix64(id) & (cap - 1), linear probing, key 0 = empty,
+ * at most cap probes, then "absent".  key / slot are caller-owned device memory
+ * that the engine reads during a call only (as hb_ent_source): after
+ * hb_move_groups the caller permutes its id column and builds again. */
+typedef struct hb_gid_dir { const uint64_t* key; const uint32_t* slot; uint64_t cap; } hb_gid_dir;
+/* Clears key[0, cap), then inserts every non-zero gid[i] -> i (gid: device,
+ * [count]: the id of slot i, 0 = none).  *dups (device or pinned) = the ids
+ * that were present already when inserted: such an id maps to one of its slots,
+ * and the caller treats *dups > 0 as an error.  The table's layout depends on
+ * the order of the inserts and is unspecified; lookups are not.  HB_EINVAL
+ * before any device work: a NULL handle or array, cap not a power of two, cap <
+ * 64 or cap < 2 x count.  Three launches (clear, insert, the count), asynchronous on
+ * the stream hb_decode uses. */
+int  hb_gid_dir_build(hb_handle* h, const uint64_t* gid, uint32_t count, uint64_t* key, uint32_t* slot,
+                      uint64_t cap, uint32_t* dups);
+
+/* The index frames of a binned batch: `binned`, bin_off from hb_egress_bin, off
+ * and status from hb_encode / hb_encode_ents of it, span from hb_peer_spans,
+ * gid = device [capacity] (the id of every slot, 0 = unset).  Reads group and
+ * to of the batch, off, status, bin_off, span and gid, and no message byte; the
+ * record count is bin_off[n_peers + 1].  ispan[b], b in [0, n_peers + 1] = the
+ * bytes of the frames of the bins before b (ispan[n_peers] = ispan[n_peers + 1]
+ * = the total: bin n_peers, "other", never gets a frame).  When the total
+ * exceeds index_cap no byte of `index` is written (ispan and fstat are): call
+ * again.  fstat[b], b in [0, n_peers) = the bin's hole count, or 0xFFFFFFFF for
+ * a bin with a record of 2^31 bytes or more, which no len word holds: its
+ * header is written with magic 0 (a receiver rejects it) and its rows are
+ * unspecified; fstat[n_peers] = 0.  seq is copied into every header.  index:
+ * device memory at a multiple of 8; ispan / fstat: device or pinned.  A bin_off
+ * that does not ascend or ends past max_batch x (max_replicas + 4) is read as
+ * an empty batch.  HB_EINVAL before any device work: a NULL argument (index
+ * with index_cap > 0), a misaligned index, no node table set.  Asynchronous on
+ * the handle's stream. */
+int  hb_frame(hb_handle* h, const hb_out_batch* binned, const uint64_t* off, const uint8_t* status,
+              const uint64_t* bin_off, const uint64_t* span, const uint64_t* gid /* device [capacity] */,
+              uint64_t self_id, uint64_t seq, uint8_t* index, uint64_t index_cap,
+              uint64_t* ispan /* [n_peers + 2] */, uint32_t* fstat /* [n_peers + 1] */);
+
+/* n_frames received frames -> the record arrays of hb_decode_follow.  Frame k
+ * is index[index_off, index_off + index_len) with its bytes at [bytes_off,
+ * bytes_off + bytes_len) of the buffer the caller will decode, and came from
+ * node `from`; `frames` is host memory, read during the call.  rows_k =
+ * hb_frame_rows(index_len); its rows take output positions [base_k, base_k +
+ * rows_k) in the caller's frame order, n = the sum.  fstatus[k] (device or
+ * pinned): */
+#define HB_FRAME_OK         0  /* the frame passed every check                                    */
+#define HB_FRAME_BAD_MAGIC  1  /* the magic or the flags are wrong                                */
+#define HB_FRAME_BAD_COUNT  2  /* the header's count differs from rows_k                          */
+#define HB_FRAME_BAD_ROUTE  3  /* to != self_id, or from != frames[k].from                        */
+#define HB_FRAME_BAD_LENGTH 4  /* the header's bytes, or the 64-bit sum of the rows' lengths (holes
+                                  included), differ from bytes_len                                */
+/* (the first that applies, in this order; a frame of no rows is OK when
+ * bytes_len is 0 and BAD_LENGTH otherwise).  Every row of a bad frame becomes
+ * off = 0, len = 0, group = 0xFFFFFFFF.  In a good frame off = bytes_off + the
+ * sum of the lengths of the rows before it, so every offset lies inside the
+ * frame's byte range; a delivered row has len = its length and group = the
+ * directory's slot; a dropped row has len = 0 and group = 0xFFFFFFFF, which
+ * hb_decode_follow drops: a hole, a gid of 0, or a gid absent from the directory
+ * (the reference's "no such group: ignore", raft/multinode.go:233-237).
+ * *n_unknown (device or pinned) = the rows dropped for an absent gid.  No
+ * payload byte is read: malformed payload is hb_decode_follow's business.
+ * off / len / group: device memory, n elements; index: device memory at a
+ * multiple of 8.  bytes_size bounds the byte ranges only, so offsets past 2^32
+ * are fine.  HB_EINVAL before any device work: a NULL handle or array (index /
+ * off / len / group may be NULL when n = 0), index_off not a multiple of 8, a
+ * range outside index_size or bytes_size, an index_len no row count gives, n !=
+ * the sum of rows_k, n > max_batch, n_frames > 256, a directory whose cap is no
+ * power of two.  n = 0 and n_frames = 0 are legal.  Asynchronous on the stream
+ * hb_decode uses; hb_decode_follow(h, bytes, off, len, group, n, ...) and
+ * hb_step follow unchanged. */
+typedef struct hb_frame_in { uint64_t index_off, index_len, bytes_off, bytes_len, from; } hb_frame_in;
+int  hb_unframe(hb_handle* h, const uint8_t* index, uint64_t index_size, const hb_frame_in* frames /* host */,
+                uint32_t n_frames, uint64_t self_id, const hb_gid_dir* dir, uint64_t bytes_size,
+                uint64_t* off, uint32_t* len, uint32_t* group, uint64_t n,
+                uint32_t* fstatus /* [n_frames] */, uint64_t* n_unknown);
+
 /* ---- the hot path ----------------------------------------------------------
  * Step one batch (all messages of the batch, per group in arrival order).
  * Asynchronous on the handle's stream.  Events and statistics of the step
