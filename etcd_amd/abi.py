@@ -115,6 +115,7 @@ HB_WIRE_BADGROUP = 5
 HB_DECODE_FOLLOW = 1      # hb_decode_caps bit: hb_decode_follow
 HB_ENCODE_ENTS = 1        # hb_encode_caps bit: hb_encode_ents
 HB_FRAME_V1 = 1           # hb_frame_caps bit: hb_frame / hb_unframe / hb_gid_dir_build
+HB_EGRESS_LIMIT_V1 = 1    # hb_egress_limit_caps bit: hb_set_egress_limit / hb_egress_limit
 # hb_unframe's fstatus
 HB_FRAME_OK = 0
 HB_FRAME_BAD_MAGIC = 1

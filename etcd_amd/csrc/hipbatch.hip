@@ -4376,6 +4376,7 @@ struct EgressArgs {
   // below the current-term run and its term (HB_LT_UNKNOWN: not known to the device)
   const uint64_t *commit0, *bl0, *blt0;
   uint64_t max_msg_size;
+  const uint64_t *szx, *szlo;  // CUT only (else null): the groups' size rings as they stand at hb_egress
   uint32_t* ccnt;    // [nc] records per chunk
   uint64_t* cbase;   // [nc + 1] their exclusive scan, then the total
   uint64_t cap;
@@ -4459,14 +4460,48 @@ __global__ void __launch_bounds__(1024) k_eg_small(EgressArgs a) {
   }
 }
 
-template <bool VOTES, bool APPS>
+// CUT (hb_set_egress_limit on an append-mode handle with a finite max_msg_size):
+// a MsgApp with entries takes limitSize's cut from the group's size ring instead of the flag,
+// unless the ring no longer holds cum(x) or the group has a follower append / restore anywhere in
+// the call's events.  The record count of a word does not depend on it, so the count kernels do
+// not take the parameter.
+template <bool VOTES, bool APPS, bool CUT>
 __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
+  static_assert(APPS || !CUT, "the cut is a MsgApp's");
   __shared__ uint64_t s_w[EG_TILE];
   __shared__ uint32_t s_pos[EG_TILE];
   __shared__ uint4 s_key[EG_TILE / 16];
   __shared__ uint32_t sh16[16];
   const uint32_t tid = threadIdx.x, part = blockIdx.x, g = part * PART + tid;
   const bool live = g < a.G;
+  // CUT: the group's size ring as it stands now (rule (i)), read once: the replay below visits a
+  // wave's sends one lane at a time, and a load there would be waited for at every visit.  The
+  // extent word is 0 where the ring cannot be trusted (rule (ii): the in-order replay has no
+  // look-ahead, so the partition's words are read once before it; a plain same-value byte store)
+  uint64_t sx = 0, slo = 0;
+  if (CUT) {
+    if (live) {
+      sx = a.szx[g];
+      slo = a.szlo[g];
+    }
+    __shared__ uint8_t s_fol[256];  // by a word's group byte
+    static_assert(PART <= 256, "a word's group byte names a lane of the partition");
+    for (uint32_t i = tid; i < 256; i += PART) s_fol[i] = 0;
+    __syncthreads();
+    for (uint32_t c = 2 * part; c < 2 * part + 2; ++c) {
+      const uint32_t n = a.ev_counts[c];
+      const uint64_t* src = a.ev + a.ev_off[c];
+      for (uint32_t i = tid; i < n; i += PART) {
+        const uint64_t w = src[i];
+        const uint32_t aux = (uint32_t)(w >> 12) & 0xF;
+        // (an EVC_CONT word has another type: its bits 4.. are value bits, its group byte is 0)
+        if (((uint32_t)w & 0xF) == HB_EV_FOLLOW && (aux == HB_FOLLOW_APPEND || aux == HB_FOLLOW_RESTORE))
+          s_fol[(uint32_t)(w >> 16) & 0xFF] = 1;
+      }
+    }
+    __syncthreads();
+    if (s_fol[tid] != 0) sx = 0;
+  }
   uint64_t term = live ? a.term0[g] : 0ull, last = live ? a.last0[g] : 0ull;
   uint64_t lt = 0;  // VOTES: raftLog.lastTerm() at this point of the replay, or HB_LT_UNKNOWN
   if (VOTES || APPS) lt = live ? a.lterm0[g] : 0ull;
@@ -4564,7 +4599,11 @@ __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
               const bool ents = xv < last;  // entries (x, L]
               uint64_t L = 0;
               if (ents) {
-                if (a.max_msg_size == HB_NO_LIMIT) L = last;
+                if (CUT) {  // (launched only under a finite limit) limitSize's cut, from the ring
+                  if (sx == 0 || xv < slo) host = true;
+                  else if (xv + 1 == last) L = last;  // the first entry always goes: no sum is read
+                  else if (!host) L = sz_cut(sx, a.max_msg_size, xv + 1, last);
+                } else if (a.max_msg_size == HB_NO_LIMIT) L = last;
                 else if (a.max_msg_size == 0) L = xv + 1;
                 else host = true;  // limitSize's cut: no event carries it
               }
@@ -5665,6 +5704,7 @@ struct hb_handle {
   // wire egress (hb_set_egress / hb_egress / hb_encode): nothing of it exists while egress is off
   bool egress = false;
   bool eg_stepped = false;        // a step or tick has run since hb_set_egress(on)
+  bool eg_limit = false;          // hb_set_egress_limit: limitSize's cut at hb_egress (§3.23)
   bool eg_votes = false;          // HB_EGRESS_VOTES: MsgVote records, the lterm0 column
   Dev<uint64_t> lterm0;           // [G] raftLog.lastTerm() before the last step / tick, or HB_LT_UNKNOWN
   bool eg_apps = false;           // HB_EGRESS_APPS: MsgApp records; lterm0 and the three columns below
@@ -7138,6 +7178,23 @@ int hb_egress_mode(hb_handle* h) {
 
 int hb_egress_caps(void) { return HB_EGRESS_ON | HB_EGRESS_VOTES | HB_EGRESS_APPS; }
 
+int hb_set_egress_limit(hb_handle* h, int on) {
+  if (!h) return HB_EINVAL;
+  const bool want = on != 0;
+  if (want == h->eg_limit) return HB_OK;
+  if (h->egress) {  // as a mode change: an hb_egress may be in flight, and the step before has no say
+    DeviceGuard guard(h->device);
+    HB_CHECK(hipStreamSynchronize(h->stream));
+    h->eg_stepped = false;
+  }
+  h->eg_limit = want;
+  return HB_OK;
+}
+
+int hb_egress_limit(hb_handle* h) { return h ? (h->eg_limit ? 1 : 0) : HB_EINVAL; }
+
+int hb_egress_limit_caps(void) { return HB_EGRESS_LIMIT_V1; }
+
 int hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t cap, uint64_t* count) {
   (void)self_id;  // m.From: hb_encode writes it; the batch holds no sender
   if (!h || !out || !count) return HB_EINVAL;
@@ -7166,6 +7223,9 @@ int hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t 
   ea.bl0 = h->bl0.get();
   ea.blt0 = h->blt0.get();
   ea.max_msg_size = h->max_msg_size;
+  const bool cut = h->eg_limit && h->eg_apps && sz_on(h->max_msg_size);
+  ea.szx = cut ? h->st.szx : nullptr;
+  ea.szlo = cut ? h->st.szlo : nullptr;
   ea.ccnt = h->eg_cnt.get();
   ea.cbase = h->eg_base.get();
   ea.cap = cap;
@@ -7180,20 +7240,24 @@ int hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t 
   ea.o_hint = out->hint;
   const bool small = ea.nc <= EG_SMALL && !h->no_small;
   // (the instantiations without APPS are the ones a handle without the bit always ran)
-#define EG_LAUNCH(V, A)                                                                              \
+  // (a word's record count does not depend on the cut: the count kernels are append mode's)
+#define EG_LAUNCH(V, A, C)                                                                           \
   do {                                                                                               \
     if (small) hipLaunchKernelGGL((k_eg_small<V, A>), dim3(1), dim3(1024), 0, h->stream, ea);       \
     else {                                                                                           \
       hipLaunchKernelGGL((k_eg_count<V, A>), dim3(ea.nc), dim3(256), 0, h->stream, ea);             \
       hipLaunchKernelGGL(k_eg_scan, dim3(1), dim3(1024), 0, h->stream, ea);                         \
     }                                                                                                \
-    hipLaunchKernelGGL((k_egress<V, A>), dim3(h->NB), dim3(PART), 0, h->stream, ea);                \
+    hipLaunchKernelGGL((k_egress<V, A, C>), dim3(h->NB), dim3(PART), 0, h->stream, ea);             \
   } while (0)
-  if (h->eg_apps) {
-    if (h->eg_votes) EG_LAUNCH(true, true);
-    else EG_LAUNCH(false, true);
-  } else if (h->eg_votes) EG_LAUNCH(true, false);
-  else EG_LAUNCH(false, false);
+  if (cut) {
+    if (h->eg_votes) EG_LAUNCH(true, true, true);
+    else EG_LAUNCH(false, true, true);
+  } else if (h->eg_apps) {
+    if (h->eg_votes) EG_LAUNCH(true, true, false);
+    else EG_LAUNCH(false, true, false);
+  } else if (h->eg_votes) EG_LAUNCH(true, false, false);
+  else EG_LAUNCH(false, false, false);
 #undef EG_LAUNCH
   return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
 }

@@ -238,6 +238,20 @@ __device__ __forceinline__ uint64_t sz_limit(const DevState& S, uint32_t g, uint
   }
   return lo;
 }
+// sz_limit's search for hb_egress's replay of a send, which has the extent word
+// in a register and has made its own test against szlo: the same arithmetic over the ring of
+// extent word x, which holds cum(next - 1) .. cum(last).  (Kept beside sz_limit rather than
+// called by it: the lanes' code stays what it was, instruction for instruction.)
+__device__ __forceinline__ uint64_t sz_cut(uint64_t x, uint64_t max_size, uint64_t next, uint64_t last) {
+  const uint64_t base = *cum_at(x, next - 1);
+  uint64_t lo = next, hi = last;
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo + 1) / 2;
+    if (*cum_at(x, mid) - base <= max_size) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
 
 // ---- term runs (follower side) ---------------------------------------------------
 // The log's runs below the current-term run, oldest first, as a ring of

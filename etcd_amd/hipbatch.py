@@ -127,6 +127,9 @@ def lib():
         "hb_set_egress": (C.c_int, [H, C.c_int]),
         "hb_egress_mode": (C.c_int, [H]),
         "hb_egress_caps": (C.c_int, []),
+        "hb_set_egress_limit": (C.c_int, [H, C.c_int]),
+        "hb_egress_limit": (C.c_int, [H]),
+        "hb_egress_limit_caps": (C.c_int, []),
         "hb_egress": (C.c_int, [H, C.c_uint64, P(abi.hb_out_batch), C.c_uint64, C.c_void_p]),
         "hb_encode": (C.c_int, [H, P(abi.hb_out_batch), C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -449,6 +452,20 @@ class Engine:
         if m < 0:
             raise HipBatchError("hb_egress_mode", m)
         return m
+
+    def set_egress_limit(self, on=True):
+        """hb_set_egress_limit: in append mode under a finite max_msg_size, a MsgApp record
+        with entries carries limitSize's cut (HB_OUT_ENTS, hint = the last entry sent) where
+        the device can prove it, instead of HB_OUT_HOST.  egress() then runs before any call
+        that rewrites a group's size ring (load_entry_sizes, load / remove / move groups)."""
+        _check("hb_set_egress_limit", lib().hb_set_egress_limit(self.h, 1 if on else 0))
+
+    def egress_limit(self):
+        """hb_egress_limit: whether the knob is on."""
+        v = lib().hb_egress_limit(self.h)
+        if v < 0:
+            raise HipBatchError("hb_egress_limit", v)
+        return bool(v)
 
     @staticmethod
     def _out_batch(out):

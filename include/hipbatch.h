@@ -645,6 +645,34 @@ int  hb_egress_mode(hb_handle* h);
 /* The mode bits this library knows (HB_EGRESS_ON | HB_EGRESS_VOTES | HB_EGRESS_APPS): append
  * mode is an addition inside ABI 8 too, and a library that lacks this function lacks it. */
 int  hb_egress_caps(void);
+/* limitSize's cut in append mode (inside ABI 8, a knob of
+ * its own so that hb_egress_mode / hb_egress_caps keep their values).  Off (the
+ * default): under a finite non-zero max_msg_size every MsgApp record with
+ * entries is HB_OUT_HOST, and every output of every call is what it was before
+ * the knob existed.  On, on a handle in append mode whose max_msg_size is
+ * finite and non-zero: such a record is an HB_OUT_ENTS record with hint = L,
+ * the last entry limitSize lets through (raft/util.go:97-110: the first entry
+ * of (index, last] always, every further one while the sum of Entry.Size()
+ * stays <= max_msg_size), read at hb_egress from the group's ring of
+ * cumulative sizes.  The record stays HB_OUT_HOST where that read cannot be
+ * proven to be the send's: (i) the ring no longer holds the sum at `index`
+ * (later appends or hb_set_log_bounds moved its oldest index past it, or the
+ * group's sizes were never loaded); (ii) the group has a follower append or
+ * restore (HB_EV_FOLLOW with aux APPEND / RESTORE) anywhere in the same call,
+ * before or after the send, which may have rewritten the ring.  The other
+ * reasons to flag a record, and every other column, are unchanged; with
+ * max_msg_size 0 or HB_NO_LIMIT, or without append mode, the knob changes
+ * nothing.  Precondition while on: hb_egress runs before any call that rewrites
+ * a group's size ring (hb_load_entry_sizes, hb_load_groups, hb_remove_groups,
+ * hb_move_groups), as it already runs before the next step; hb_reserve_log
+ * keeps the contents and may come first.  A change of the knob while egress is
+ * on waits for the stream, and hb_egress gives count 0 until the next step or
+ * tick, as a mode change does.  hb_egress_limit returns 0 or 1, HB_EINVAL for a
+ * NULL handle; a library that lacks hb_egress_limit_caps lacks the knob. */
+#define HB_EGRESS_LIMIT_V1 1
+int  hb_set_egress_limit(hb_handle* h, int on);
+int  hb_egress_limit(hb_handle* h);
+int  hb_egress_limit_caps(void);         /* the cut features this library knows: HB_EGRESS_LIMIT_V1 */
 /* A vote record whose LogTerm the device cannot tell: info carries this flag
  * and log_term = 0; the host builds the message from its event as before.
  * Likewise a MsgApp record of append mode whose LogTerm, Commit or entry range

@@ -18,6 +18,11 @@ Workloads on a handle of 1,048,576 groups x 3:
           proposal and two acks per group, so every group sends four MsgApp,
           two with the new entry (spliced by the host) and two with only the
           new Commit; every group's older term run is loaded, as a node's are.
+          With --max-msg-size N the handle has that finite MaxSizePerMsg and
+          hb_set_egress_limit is on: every group's last entry
+          has a size loaded and every proposed entry a random descriptor, as
+          synth.window_sizes / attach_entry_descs make them, and each MsgApp
+          with entries takes limitSize's cut from the group's size ring.
 
 Per workload: the step (or tick) runs once with egress on, then hb_egress +
 hb_encode (chained through the device-resident count, no host sync between
@@ -38,6 +43,7 @@ back-to-back steps of the follow and the cfg2 workload with egress off, on
   python tools/microbench/egress_bench.py [--out profiles/egress_bench.json]
   python tools/microbench/egress_bench.py --workload campaign [--out profiles/egress_vote_bench.json]
   python tools/microbench/egress_bench.py --workload cfg2 [--out profiles/egress_app_bench.json]
+  python tools/microbench/egress_bench.py --workload cfg2 --max-msg-size 1048576
 """
 import argparse
 import json
@@ -136,6 +142,21 @@ def load_one_older_run(eng, g):
     assert rc == abi.HB_OK, rc
 
 
+def load_last_sizes(eng, g, seed, max_len=64):
+    """hb_load_entry_sizes for every group at once: Entry.Size() of its last entry, a random
+    payload as synth.window_sizes draws them (the ring then keeps its minimum capacity; a cfg2
+    step sends from the last index, which the ring always holds)."""
+    from etcd_amd import hipbatch
+    n = len(g)
+    rng = np.random.default_rng(seed)
+    ln = rng.integers(0, max_len + 1, n).astype(np.uint64)
+    has = rng.random(n) >= 0.2
+    z = 4 + synth._sov(g["term"]) + synth._sov(g["last_index"]) + np.where(has, 1 + ln + synth._sov(ln), 0)
+    gs, ns, z = np.arange(n, dtype=np.uint32), np.ones(n, dtype=np.uint32), z.astype(np.uint32)
+    rc = hipbatch.lib().hb_load_entry_sizes(eng.h, n, gs.ctypes.data, ns.ctypes.data, z.ctypes.data)
+    assert rc == abi.HB_OK, rc
+
+
 def snapshot_modes(torch, stream, eng, one, steps, name):
     """ms per step of `one` with egress off, then mode 1, then mode 5 (K back-to-back steps each)."""
     span = 5 + steps
@@ -169,18 +190,26 @@ def cfg2_main(args, torch, stream):
     # ---- cfg2 steps: egress off / mode 1 / mode 5, then one step's hb_egress + hb_encode -------
     seed = 0x5EED0002
     g, _ = synth.steady_groups(G, N, seed=seed, with_runs=False)
-    eng = Engine(G, max_replicas=N, max_inflight=W, max_batch=2 * G, stream=stream)
+    limit = args.max_msg_size
+    eng = Engine(G, max_replicas=N, max_inflight=W, max_batch=2 * G, stream=stream,
+                 **(dict(max_msg_size=limit) if limit else {}))
     eng.load_groups(g)
     eng.load_peers(peers())
     load_one_older_run(eng, g)
     b0 = synth.cfg2_batch(g, 0, seed=seed)  # step k acks last + k + 1 (the same arrival order every step)
     x = {k: dv(torch, b0[k]) for k in ("group", "info", "term", "index", "props")}
+    sized = {}
+    if limit:  # the same descriptors every step: one proposed entry per group
+        load_last_sizes(eng, g, seed + 1)
+        bd = synth.attach_entry_descs(b0, G, seed=seed + 2)
+        sized = {k: dv(torch, bd[k]) for k in ("edesc", "eoff", "peoff")}
+        eng.set_egress_limit(True)
 
     def cfg2(k):
-        eng.step(x["group"], x["info"], x["term"], x["index"] + k, None, x["props"], host=False)
+        eng.step(x["group"], x["info"], x["term"], x["index"] + k, None, x["props"], host=False, **sized)
     snapshot.append(snapshot_modes(torch, stream, eng, cfg2, args.steps, "cfg2"))
     print(json.dumps(snapshot), flush=True)
-    assert eng.egress_mode() == abi.HB_EGRESS_ON | abi.HB_EGRESS_APPS
+    assert eng.egress_mode() == abi.HB_EGRESS_ON | abi.HB_EGRESS_APPS and eng.egress_limit() == bool(limit)
     cfg2(3 * (5 + args.steps))
     sink = Sink(torch, 4 * G)
     us = timed(torch, stream, eng, sink, args.reps)
@@ -195,6 +224,7 @@ def cfg2_main(args, torch, stream):
     assert r["records"] == 4 * G and ((info & 0xF) == abi.HB_MSG_APP).all()
     assert r["records_spliced"] == r["records_entries_flag"] == 2 * G and r["records_flagged"] == 0
     assert (status[info & abi.HB_OUT_ENTS == 0] == abi.HB_WIRE_OK).all()
+    r["max_msg_size"] = limit
     results.append(r)
     eng.close()
     return dict(bench="hb_egress + hb_encode, append mode", results=results, snapshot_cost=snapshot)
@@ -206,6 +236,8 @@ def main():
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--workload", choices=("egress", "campaign", "cfg2"), default="egress")
+    ap.add_argument("--max-msg-size", type=int, default=0,
+                    help="cfg2 only: a finite MaxSizePerMsg, with hb_set_egress_limit on (0: no limit, the default)")
     args = ap.parse_args()
     import torch
     stream = torch.cuda.Stream()
