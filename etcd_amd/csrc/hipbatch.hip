@@ -3225,6 +3225,9 @@ struct DecfArgs {
   uint32_t* bsum;   // [workgroups of k_decf_parse] entries per workgroup
   uint64_t* bbase;  // [workgroups + 1] their exclusive scan, then the total
 };
+// PROPS (hb_set_wire_props bit HB_WIRE_PROPS_IN): a canonical forwarded MsgProp is
+// a batch record too.  A template parameter of the kernels that parse, so that with the bit off
+// the code that runs is the code a handle without the knob ran.
 constexpr uint32_t DECF_WIN = 8192;  // bytes staged per wave: 128 a record (a MsgApp with one small entry is ~70)
 constexpr uint32_t DECF_SMALL_MAX = 16384;  // the small-step rule: scan and write in one workgroup
 static_assert(WI_ENT_MAX_DATA == HB_ENT_MAX_DATA && (uint64_t)DEC_THREADS * WI_MAX_ENTS < (1ull << 32),
@@ -3235,13 +3238,16 @@ static_assert((DEC_THREADS / 64) * (DECF_WIN + 32) <= 40 * 1024, "four workgroup
 // Outcome of one record -> batch record + status (both passes).  nent: the
 // field-7 occurrences; canon: the record has the canonical shape and its
 // entries pass the checks.  Returns whether the record keeps an entry run.
+template <bool PROPS>
 __device__ __forceinline__ bool decf_emit(const DecfArgs& a, uint64_t k, int rc, const WireMsgF& f, bool canon,
                                           uint32_t g, bool gok, const uint64_t* ids) {
   const WireMsg& m = f.m;
   const bool resp = m.type == HB_MSG_APP_RESP || m.type == HB_MSG_VOTE_RESP || m.type == HB_MSG_HEARTBEAT_RESP;
   const bool fol = m.type == HB_MSG_APP || m.type == HB_MSG_HEARTBEAT || m.type == HB_MSG_VOTE;
+  // a forwarded proposal that passed wi_message's proposal rule (pass one only: canon)
+  const bool prop = PROPS && canon && m.type == HB_MSG_PROP;
   uint32_t slot = HB_SLOT_NONE;
-  if (rc == W_OK && (resp || fol) && gok && a.d.peer && m.from != 0) {
+  if (rc == W_OK && (resp || fol || prop) && gok && a.d.peer && m.from != 0) {
     const uint32_t nn = (uint32_t)ids[HB_PEER_ROW - 1];
 #pragma unroll
     for (uint32_t s = 0; s < HB_MAX_REPLICAS; ++s)
@@ -3255,6 +3261,7 @@ __device__ __forceinline__ bool decf_emit(const DecfArgs& a, uint64_t k, int rc,
            m.type == HB_MSG_SNAP_STATUS)
     st = HB_WIRE_LOCAL;  // IsLocalMsg raft/util.go:49-51
   else if (resp) st = gok ? HB_WIRE_OK : HB_WIRE_BADGROUP;
+  else if (prop) st = gok ? HB_WIRE_OK : HB_WIRE_HOST;  // index = the entry count; a non-member's slot is HB_SLOT_NONE
   else if (!fol || !gok) st = HB_WIRE_HOST;  // (hb_decode's precedence: the type rule comes before the group's)
   else if (m.type == HB_MSG_VOTE) st = slot != HB_SLOT_NONE ? HB_WIRE_OK : HB_WIRE_HOST;  // HB_INFO_VOTED: the host's
   else if (m.type == HB_MSG_APP) st = (f.f.nentries == 0 || canon) ? HB_WIRE_OK : HB_WIRE_HOST;
@@ -3268,18 +3275,19 @@ __device__ __forceinline__ bool decf_emit(const DecfArgs& a, uint64_t k, int rc,
   a.d.o_group[k] = ok ? g : 0xFFFFFFFFu;
   a.d.o_info[k] = ok ? ((uint32_t)m.type | (slot << 4) | ((uint32_t)m.reject << 8)) : 0u;
   a.d.o_term[k] = ok ? m.term : 0ull;
-  a.d.o_index[k] = ok ? m.index : 0ull;
-  a.d.o_hint[k] = ok ? hint : 0ull;
+  a.d.o_index[k] = ok ? (prop ? (uint64_t)f.f.nentries : m.index) : 0ull;
+  a.d.o_hint[k] = ok ? hint : 0ull;  // (a proposal's header is all zero: wi_message)
   a.o_commit[k] = ok ? commit : 0ull;
   a.d.status[k] = (uint8_t)st;
-  return ok && m.type == HB_MSG_APP && f.f.nentries != 0;
+  return ok && (m.type == HB_MSG_APP || prop) && f.f.nentries != 0;
 }
 
+template <bool PROPS>
 __device__ __forceinline__ bool decf_canon(const uint8_t* p, uint32_t len, WireMsgF* f) {
   WiHeader h;
   WiTail t;
   uint32_t ne = 0;
-  if (!wi_message(p, len, &h, &t, &ne)) return false;
+  if (!wi_message(p, len, &h, &t, &ne, PROPS)) return false;
   f->m.type = (int32_t)h.type;
   f->m.from = h.from;
   f->m.term = h.term;
@@ -3292,6 +3300,7 @@ __device__ __forceinline__ bool decf_canon(const uint8_t* p, uint32_t len, WireM
   return true;
 }
 
+template <bool PROPS>
 __global__ void __launch_bounds__(DEC_THREADS) k_decf_parse(DecfArgs a, uint32_t* q, uint32_t* qn) {
   __shared__ uint4 l_win[DEC_THREADS / 64][DECF_WIN / 16 + 2];
   __shared__ uint32_t sh16[16];
@@ -3338,7 +3347,7 @@ __global__ void __launch_bounds__(DEC_THREADS) k_decf_parse(DecfArgs a, uint32_t
     // a wave whose span does not fit (a long payload among its records) parses from global memory:
     // one copy of the parser behind a flat pointer, chosen per wave
     const uint8_t* src = fits ? win + (reinterpret_cast<uintptr_t>(A_.bytes) + o - base) : A_.bytes + o;
-    canon = decf_canon(src, len, &f);
+    canon = decf_canon<PROPS>(src, len, &f);
   }
   // wave-aggregated append of the other records to the general pass's queue
   const bool slowl = live && !canon;
@@ -3352,7 +3361,7 @@ __global__ void __launch_bounds__(DEC_THREADS) k_decf_parse(DecfArgs a, uint32_t
     if (slowl) q[b0 + (uint32_t)__popcll(slow & ((1ull << lane) - 1))] = (uint32_t)k;
   }
   uint32_t ne = 0;
-  if (canon && decf_emit(a, k, W_OK, f, true, g, gok, reinterpret_cast<const uint64_t*>(prow))) ne = f.f.nentries;
+  if (canon && decf_emit<PROPS>(a, k, W_OK, f, true, g, gok, reinterpret_cast<const uint64_t*>(prow))) ne = f.f.nentries;
   uint32_t tot;
   const uint32_t ex = block_excl_scan(ne, sh16, &tot);
   if (live) a.eoff[k] = ex;
@@ -3373,7 +3382,7 @@ __global__ void __launch_bounds__(DEC_THREADS) k_decf_general(DecfArgs a, const 
     }
     WireMsgF f;
     const int rc = w_unmarshal_follow(a.d.bytes + a.d.off[k], (int64_t)a.d.len[k], &f);
-    (void)decf_emit(a, k, rc, f, false, g, gok, ids);
+    (void)decf_emit<false>(a, k, rc, f, false, g, gok, ids);  // (a queued record is no proposal record)
   }
   // qn[1] counts finished workgroups; the last one resets both words
   __syncthreads();
@@ -3426,6 +3435,7 @@ __device__ __forceinline__ void decf_finish(const DecfArgs& a, uint64_t tot) {
 // Workgroup `blk` of k_decf_parse, whose first entry is `base`: the final eoff,
 // and the entry runs when `write` (uniform).  eoff is rewritten in place: every
 // lane reads its own and its neighbour's local prefix before any lane writes.
+template <bool PROPS>
 __device__ __forceinline__ void decf_write_block(const DecfArgs& a, uint64_t blk, uint64_t base, bool write) {
   const uint64_t n = a.d.n, k = blk * DEC_THREADS + threadIdx.x;
   const bool live = k < n;
@@ -3447,7 +3457,11 @@ __device__ __forceinline__ void decf_write_block(const DecfArgs& a, uint64_t blk
   uint64_t i = h.ents;
   for (uint64_t j = 0; j < ne; ++j) {
     WiEntry e;
-    if (!wi_entry(p, l, i, h.index + 1 + j, &e)) return;
+    if constexpr (PROPS) {  // the entry rule pass one used
+      if (!(wi_is_prop(h, true) ? wi_prop_entry(p, l, i, &e) : wi_entry(p, l, i, h.index + 1 + j, &e))) return;
+    } else {
+      if (!wi_entry(p, l, i, h.index + 1 + j, &e)) return;
+    }
     a.eterm[e0 + j] = e.term;
     a.edesc[e0 + j] = e.desc;
     a.edata[e0 + j] = e.data ? o + e.data : 0ull;
@@ -3470,10 +3484,12 @@ __global__ void __launch_bounds__(1024) k_decf_scan(DecfArgs a, uint32_t nblk) {
     decf_finish(a, tot);
   }
 }
+template <bool PROPS>
 __global__ void __launch_bounds__(DEC_THREADS) k_decf_write(DecfArgs a, uint32_t nblk) {
-  decf_write_block(a, blockIdx.x, a.bbase[blockIdx.x], a.bbase[nblk] <= a.ent_cap);
+  decf_write_block<PROPS>(a, blockIdx.x, a.bbase[blockIdx.x], a.bbase[nblk] <= a.ent_cap);
 }
 // At most DECF_SMALL_MAX records (at most DEC_THREADS workgroups of k_decf_parse): scan and write.
+template <bool PROPS>
 __global__ void __launch_bounds__(DEC_THREADS) k_decf_small(DecfArgs a, uint32_t nblk) {
   __shared__ uint64_t sh16[16];
   __shared__ uint64_t l_base[DEC_THREADS];
@@ -3481,7 +3497,7 @@ __global__ void __launch_bounds__(DEC_THREADS) k_decf_small(DecfArgs a, uint32_t
   l_base[threadIdx.x] = block_excl_scan64(threadIdx.x < nblk ? (uint64_t)a.bsum[threadIdx.x] : 0ull, sh16, &tot);
   __syncthreads();
   if (threadIdx.x == 0) decf_finish(a, tot);
-  for (uint32_t b = 0; b < nblk; ++b) decf_write_block(a, b, l_base[b], tot <= a.ent_cap);
+  for (uint32_t b = 0; b < nblk; ++b) decf_write_block<PROPS>(a, b, l_base[b], tot <= a.ent_cap);
 }
 
 // ============================================================================
@@ -4201,7 +4217,8 @@ __device__ __forceinline__ uint64_t ence_load(const EnceArgs& a, uint64_t i, uin
   const uint32_t sz = enc_load(a.e, i, n, &x->r);
   x->cov = false;
   x->pos = x->ne = 0;
-  if (!x->r.ents) return sz;
+  // a MsgProp's (index, hint] is (0, arrival index], not an index range: never covered
+  if (!x->r.ents || x->r.type == HB_MSG_PROP) return sz;
   const uint32_t g = a.group[i];
   if (g >= a.capacity) return sz;
   uint64_t run = 0;
@@ -4393,10 +4410,12 @@ static_assert(EG_PER == 8, "a lane's group bytes of a tile are one 8-byte LDS st
 // The records a word makes.  VOTES (hb_set_egress bit HB_EGRESS_VOTES): campaign's MsgVotes too,
 // one for an HB_EV_VOTE word and one per slot of an EVC_VBCAST word's mask.  APPS (bit
 // HB_EGRESS_APPS): sendAppend's MsgApps too, one for an HB_EV_APP word and one per slot of an
-// EVC_BCAST word's mask.
-template <bool VOTES, bool APPS>
+// EVC_BCAST word's mask.  FWD (hb_set_wire_props bit HB_WIRE_PROPS_OUT): stepFollower's forwarded
+// MsgProp too, one for an HB_EV_PROP_FWD word.
+template <bool VOTES, bool APPS, bool FWD>
 __device__ __forceinline__ uint32_t eg_record(uint64_t w) {
   const uint32_t t = (uint32_t)w & 0xF;
+  if (FWD && t == HB_EV_PROP_FWD) return 1u;
   if (APPS) {
     if (t == EVC_BCAST) return (uint32_t)__popc((uint32_t)(w >> 4) & 0x7Fu);
     if (t == HB_EV_APP) return 1u;
@@ -4407,13 +4426,13 @@ __device__ __forceinline__ uint32_t eg_record(uint64_t w) {
   }
   return (t == HB_EV_RESP || t == HB_EV_HEARTBEAT) ? 1u : 0u;
 }
-template <bool VOTES, bool APPS>
+template <bool VOTES, bool APPS, bool FWD>
 __global__ void __launch_bounds__(256) k_eg_count(EgressArgs a) {
   __shared__ uint32_t sh16[16];
   const uint32_t c = blockIdx.x, n = a.ev_counts[c];
   const uint64_t* src = a.ev + a.ev_off[c];
   uint32_t k = 0;
-  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) k += eg_record<VOTES, APPS>(src[i]);
+  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) k += eg_record<VOTES, APPS, FWD>(src[i]);
   uint32_t tot;
   (void)block_excl_scan(k, sh16, &tot);
   if (threadIdx.x == 0) a.ccnt[c] = tot;
@@ -4435,7 +4454,7 @@ __global__ void __launch_bounds__(1024) k_eg_scan(EgressArgs a) {
   }
 }
 // Count and scan in one workgroup when the chunks are few: a wave per chunk counts.
-template <bool VOTES, bool APPS>
+template <bool VOTES, bool APPS, bool FWD>
 __global__ void __launch_bounds__(1024) k_eg_small(EgressArgs a) {
   __shared__ uint32_t sh16[16];
   __shared__ uint32_t s_cnt[EG_SMALL];
@@ -4444,7 +4463,7 @@ __global__ void __launch_bounds__(1024) k_eg_small(EgressArgs a) {
     const uint32_t n = a.ev_counts[c];
     const uint64_t* src = a.ev + a.ev_off[c];
     uint32_t k = 0;
-    for (uint32_t i = lane; i < n; i += 64) k += eg_record<VOTES, APPS>(src[i]);
+    for (uint32_t i = lane; i < n; i += 64) k += eg_record<VOTES, APPS, FWD>(src[i]);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) k += __shfl_xor(k, d);
     if (lane == 0) s_cnt[c] = k;
@@ -4465,7 +4484,7 @@ __global__ void __launch_bounds__(1024) k_eg_small(EgressArgs a) {
 // unless the ring no longer holds cum(x) or the group has a follower append / restore anywhere in
 // the call's events.  The record count of a word does not depend on it, so the count kernels do
 // not take the parameter.
-template <bool VOTES, bool APPS, bool CUT>
+template <bool VOTES, bool APPS, bool CUT, bool FWD>
 __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
   static_assert(APPS || !CUT, "the cut is a MsgApp's");
   __shared__ uint64_t s_w[EG_TILE];
@@ -4529,7 +4548,7 @@ __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
       for (uint32_t j = 0; j < EG_PER; ++j) {
         const uint32_t li = tid * EG_PER + j;
         w[j] = li < m ? src[t0 + li] : (uint64_t)EVC_CONT;
-        k += eg_record<VOTES, APPS>(w[j]);
+        k += eg_record<VOTES, APPS, FWD>(w[j]);
       }
       uint32_t tot;
       uint32_t pos = block_excl_scan(k, sh16, &tot);
@@ -4539,7 +4558,7 @@ __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
         const uint32_t li = tid * EG_PER + j;
         s_w[li] = w[j];
         s_pos[li] = pos;
-        pos += eg_record<VOTES, APPS>(w[j]);
+        pos += eg_record<VOTES, APPS, FWD>(w[j]);
         const uint32_t kb = (uint32_t)(w[j] >> 16) & 0xFF;
         if (j < 4) klo |= kb << (8 * j);
         else khi |= kb << (8 * (j - 4));
@@ -4589,7 +4608,22 @@ __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
                 cm_known = false;  // until the next HB_EV_COMMIT
               }
             } else if (type == HB_EV_FAULT) dead = true;
-            else if (APPS && (type == HB_EV_APP || type == EVC_BCAST)) {
+            else if (FWD && type == HB_EV_PROP_FWD) {
+              // stepFollower's forward (raft/raft.go:616-624): send leaves a MsgProp's Term at 0
+              // (:226-236); the entries are the host's, named by the arrival index in hint
+              const uint64_t o = run + s_pos[li];
+              if (o < a.cap) {
+                const bool slot = to <= HB_REF_SLOT_MAX;
+                a.o_group[o] = g;
+                a.o_info[o] = HB_INFO(HB_MSG_PROP, slot ? to : (uint32_t)HB_REF_OTHER, false) | (uint32_t)HB_OUT_ENTS;
+                a.o_to[o] = slot ? a.peer[(size_t)g * HB_PEER_ROW + to] : 0ull;
+                a.o_term[o] = 0;
+                a.o_log_term[o] = 0;
+                a.o_index[o] = 0;
+                a.o_commit[o] = 0;
+                a.o_hint[o] = xv;
+              }
+            } else if (APPS && (type == HB_EV_APP || type == EVC_BCAST)) {
               // sendAppend's MsgApp (raft/raft.go:261-281): one record per slot, in slot order.
               // LogTerm: the Term when the aux bit says so, the boundary's term for a send at the
               // boundary; anything the replay cannot prove leaves the record to the host.
@@ -5705,6 +5739,7 @@ struct hb_handle {
   bool egress = false;
   bool eg_stepped = false;        // a step or tick has run since hb_set_egress(on)
   bool eg_limit = false;          // hb_set_egress_limit: limitSize's cut at hb_egress (§3.23)
+  int wire_props = 0;             // hb_set_wire_props: HB_WIRE_PROPS_IN | HB_WIRE_PROPS_OUT (§3.24)
   bool eg_votes = false;          // HB_EGRESS_VOTES: MsgVote records, the lterm0 column
   Dev<uint64_t> lterm0;           // [G] raftLog.lastTerm() before the last step / tick, or HB_LT_UNKNOWN
   bool eg_apps = false;           // HB_EGRESS_APPS: MsgApp records; lterm0 and the three columns below
@@ -6645,6 +6680,7 @@ int hb_decode_follow(hb_handle* h, const uint8_t* bytes, const uint64_t* off, co
   fa.edata = edata;
   fa.ent_cap = ent_cap;
   fa.n_ent = dev_view(n_ent);
+  const bool props = (h->wire_props & HB_WIRE_PROPS_IN) != 0;
   // on the stream the batches come from, as hb_decode
   hipStream_t ds = h->in_stream_set ? h->in_stream : h->stream;
   const uint64_t nblk = (n + DEC_THREADS - 1) / DEC_THREADS;
@@ -6656,18 +6692,26 @@ int hb_decode_follow(hb_handle* h, const uint8_t* bytes, const uint64_t* off, co
   fa.bsum = h->decf_sum.get();
   fa.bbase = h->decf_base.get();
   if (nblk) {
-    hipLaunchKernelGGL(k_decf_parse, dim3((unsigned)nblk), dim3(DEC_THREADS), 0, ds, fa, h->dec_q.get(),
-                       h->dec_qn.get());
+    if (props)
+      hipLaunchKernelGGL(k_decf_parse<true>, dim3((unsigned)nblk), dim3(DEC_THREADS), 0, ds, fa, h->dec_q.get(),
+                         h->dec_qn.get());
+    else
+      hipLaunchKernelGGL(k_decf_parse<false>, dim3((unsigned)nblk), dim3(DEC_THREADS), 0, ds, fa, h->dec_q.get(),
+                         h->dec_qn.get());
     HB_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_decf_general, dim3((unsigned)(nblk < DEC_GEN_BLOCKS ? nblk : DEC_GEN_BLOCKS)), dim3(DEC_THREADS),
                        0, ds, fa, h->dec_q.get(), h->dec_qn.get());
     HB_CHECK(hipGetLastError());
   }
   if (n <= DECF_SMALL_MAX && !h->no_small) {
-    hipLaunchKernelGGL(k_decf_small, dim3(1), dim3(DEC_THREADS), 0, ds, fa, (uint32_t)nblk);
+    if (props) hipLaunchKernelGGL(k_decf_small<true>, dim3(1), dim3(DEC_THREADS), 0, ds, fa, (uint32_t)nblk);
+    else hipLaunchKernelGGL(k_decf_small<false>, dim3(1), dim3(DEC_THREADS), 0, ds, fa, (uint32_t)nblk);
   } else {
     hipLaunchKernelGGL(k_decf_scan, dim3(1), dim3(1024), 0, ds, fa, (uint32_t)nblk);
-    if (nblk) hipLaunchKernelGGL(k_decf_write, dim3((unsigned)nblk), dim3(DEC_THREADS), 0, ds, fa, (uint32_t)nblk);
+    if (nblk && props)
+      hipLaunchKernelGGL(k_decf_write<true>, dim3((unsigned)nblk), dim3(DEC_THREADS), 0, ds, fa, (uint32_t)nblk);
+    else if (nblk)
+      hipLaunchKernelGGL(k_decf_write<false>, dim3((unsigned)nblk), dim3(DEC_THREADS), 0, ds, fa, (uint32_t)nblk);
   }
   HB_CHECK(hipGetLastError());
   return HB_OK;
@@ -7195,6 +7239,22 @@ int hb_egress_limit(hb_handle* h) { return h ? (h->eg_limit ? 1 : 0) : HB_EINVAL
 
 int hb_egress_limit_caps(void) { return HB_EGRESS_LIMIT_V1; }
 
+int hb_set_wire_props(hb_handle* h, int bits) {
+  if (!h || (bits & ~(HB_WIRE_PROPS_IN | HB_WIRE_PROPS_OUT)) != 0) return HB_EINVAL;
+  if (bits == h->wire_props) return HB_OK;
+  // a configuration call: an hb_egress or hb_decode_follow may be in flight (the forward record
+  // reads no pre-step column, so the events of the step before stay good)
+  DeviceGuard guard(h->device);
+  HB_CHECK(hipStreamSynchronize(h->stream));
+  if (h->in_stream_set) HB_CHECK(hipStreamSynchronize(h->in_stream));
+  h->wire_props = bits;
+  return HB_OK;
+}
+
+int hb_wire_props(hb_handle* h) { return h ? h->wire_props : HB_EINVAL; }
+
+int hb_wire_props_caps(void) { return HB_WIRE_PROPS_IN | HB_WIRE_PROPS_OUT; }
+
 int hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t cap, uint64_t* count) {
   (void)self_id;  // m.From: hb_encode writes it; the batch holds no sender
   if (!h || !out || !count) return HB_EINVAL;
@@ -7241,14 +7301,21 @@ int hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t 
   const bool small = ea.nc <= EG_SMALL && !h->no_small;
   // (the instantiations without APPS are the ones a handle without the bit always ran)
   // (a word's record count does not depend on the cut: the count kernels are append mode's)
-#define EG_LAUNCH(V, A, C)                                                                           \
+  // (with HB_WIRE_PROPS_OUT off the instantiations are the ones a handle without the knob ran)
+  const bool fwd = (h->wire_props & HB_WIRE_PROPS_OUT) != 0;
+#define EG_LAUNCH_F(V, A, C, F)                                                                      \
   do {                                                                                               \
-    if (small) hipLaunchKernelGGL((k_eg_small<V, A>), dim3(1), dim3(1024), 0, h->stream, ea);       \
+    if (small) hipLaunchKernelGGL((k_eg_small<V, A, F>), dim3(1), dim3(1024), 0, h->stream, ea);    \
     else {                                                                                           \
-      hipLaunchKernelGGL((k_eg_count<V, A>), dim3(ea.nc), dim3(256), 0, h->stream, ea);             \
+      hipLaunchKernelGGL((k_eg_count<V, A, F>), dim3(ea.nc), dim3(256), 0, h->stream, ea);          \
       hipLaunchKernelGGL(k_eg_scan, dim3(1), dim3(1024), 0, h->stream, ea);                         \
     }                                                                                                \
-    hipLaunchKernelGGL((k_egress<V, A, C>), dim3(h->NB), dim3(PART), 0, h->stream, ea);             \
+    hipLaunchKernelGGL((k_egress<V, A, C, F>), dim3(h->NB), dim3(PART), 0, h->stream, ea);          \
+  } while (0)
+#define EG_LAUNCH(V, A, C)                 \
+  do {                                     \
+    if (fwd) EG_LAUNCH_F(V, A, C, true);   \
+    else EG_LAUNCH_F(V, A, C, false);      \
   } while (0)
   if (cut) {
     if (h->eg_votes) EG_LAUNCH(true, true, true);
@@ -7259,6 +7326,7 @@ int hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t 
   } else if (h->eg_votes) EG_LAUNCH(true, false, false);
   else EG_LAUNCH(false, false, false);
 #undef EG_LAUNCH
+#undef EG_LAUNCH_F
   return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;
 }
 

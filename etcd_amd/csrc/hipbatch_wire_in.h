@@ -11,6 +11,12 @@
 //
 //   08 Type (one byte, 00 or 01) | 10 Term | 18 Index | [ 22 len(Data) Data ] | end of its span
 //
+// and for a forwarded proposal (hb_set_wire_props bit HB_WIRE_PROPS_IN; a MsgProp whose header
+// fields 4-6, Commit, Reject and RejectHint are all 0 and which carries at least one entry) as
+// Propose makes them:
+//
+//   08 00 | 10 00 | 18 00 | [ 22 len(Data) Data ] | end of its span
+//
 // Every varint is at most 10 bytes (bits past 63 drop, as Go's shift does).  Entry k of a
 // message carries Index == m.Index + 1 + k (mod 2^64) and at most WI_ENT_MAX_DATA bytes of
 // Data.  On this shape Message.Unmarshal makes the same assignments in the same order and no
@@ -18,8 +24,8 @@
 // "not canonical" and the caller runs the general decoder (hipbatch_wire.h).
 //
 // Nothing outside d[0, l) is read.  Plain C++ with no HIP header and no intrinsic: the
-// engine compiles it for the device (hipbatch.hip) and tests/asan/wire_in_asan.cpp for the
-// host, under the sanitizers.
+// engine compiles it for the device (hipbatch.hip) and tests/asan/wire_in_asan.cpp and
+// tests/asan/wire_props_asan.cpp for the host, under the sanitizers.
 #pragma once
 #include <stdint.h>
 
@@ -123,18 +129,61 @@ WI_HD inline bool wi_tail(const uint8_t* d, uint64_t l, uint64_t i, WiTail* t) {
   return i == l;
 }
 
-// The whole record: header, the entry run (counted and checked, *ne entries), tail.
-WI_HD inline bool wi_message(const uint8_t* d, uint64_t l, WiHeader* h, WiTail* t, uint32_t* ne) {
+// One entry of a forwarded proposal's field-7 run at d[i] (the caller saw 3a there), as
+// Propose makes it (pb.Entry{Data: data}, raft/node.go; stepFollower forwards it untouched):
+//
+//   08 00 | 10 00 | 18 00 | [ 22 len(Data) Data ] | end of its span
+//
+// Type, Term and Index are the single byte 00 each; e->term = 0.  i moves past it.
+WI_HD inline bool wi_prop_entry(const uint8_t* d, uint64_t l, uint64_t& i, WiEntry* e) {
+  uint64_t span, v;
+  if (!wi_field(d, l, i, 0x3a, span)) return false;
+  if (span > l - i) return false;
+  const uint64_t end = i + span;
+  if (end - i < 6) return false;
+  const uint8_t head[6] = {0x08, 0x00, 0x10, 0x00, 0x18, 0x00};
+  bool same = true;
+  for (int j = 0; j < 6; ++j) same &= d[i + j] == head[j];
+  if (!same) return false;
+  i += 6;
+  e->term = 0;
+  if (i == end) {
+    e->desc = 0;
+    e->data = 0;
+    return true;
+  }
+  if (!wi_field(d, end, i, 0x22, v)) return false;
+  if (v > WI_ENT_MAX_DATA || v != end - i) return false;
+  e->desc = (uint32_t)v | (1u << 31);
+  e->data = i;
+  i = end;
+  return true;
+}
+
+constexpr uint32_t WI_MSG_PROP = 2;  // HB_MSG_PROP (raftpb.MsgProp)
+
+// Whether a record of this header takes the proposal rule (hb_set_wire_props bit HB_WIRE_PROPS_IN).
+WI_HD inline bool wi_is_prop(const WiHeader& h, bool props) { return props && h.type == WI_MSG_PROP; }
+
+// The whole record: header, the entry run (counted and checked, *ne entries), tail.  The entry
+// rule is the follower's (wi_entry), or with `props` for a record of type MsgProp the forwarded
+// proposal's: wi_prop_entry for every entry, at least one of them, and the header r.send writes
+// for a MsgProp (Term = LogTerm = Index = Commit = 0, no Reject, RejectHint = 0).
+WI_HD inline bool wi_message(const uint8_t* d, uint64_t l, WiHeader* h, WiTail* t, uint32_t* ne, bool props = false) {
   if (!wi_header(d, l, h)) return false;
+  const bool prop = wi_is_prop(*h, props);
+  if (prop && (h->term | h->log_term | h->index) != 0) return false;
   uint64_t i = h->ents;
   uint32_t n = 0;
   while (i < l && d[i] == 0x3a) {
     WiEntry e;
-    if (n == WI_MAX_ENTS || !wi_entry(d, l, i, h->index + 1 + n, &e)) return false;
+    if (n == WI_MAX_ENTS) return false;
+    if (!(prop ? wi_prop_entry(d, l, i, &e) : wi_entry(d, l, i, h->index + 1 + n, &e))) return false;
     ++n;
   }
   *ne = n;
-  return wi_tail(d, l, i, t);
+  if (!wi_tail(d, l, i, t)) return false;
+  return !prop || (n != 0 && t->commit == 0 && !t->reject && t->hint == 0);
 }
 
 }  // namespace hb

@@ -130,6 +130,9 @@ def lib():
         "hb_set_egress_limit": (C.c_int, [H, C.c_int]),
         "hb_egress_limit": (C.c_int, [H]),
         "hb_egress_limit_caps": (C.c_int, []),
+        "hb_set_wire_props": (C.c_int, [H, C.c_int]),
+        "hb_wire_props": (C.c_int, [H]),
+        "hb_wire_props_caps": (C.c_int, []),
         "hb_egress": (C.c_int, [H, C.c_uint64, P(abi.hb_out_batch), C.c_uint64, C.c_void_p]),
         "hb_encode": (C.c_int, [H, P(abi.hb_out_batch), C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -466,6 +469,22 @@ class Engine:
         if v < 0:
             raise HipBatchError("hb_egress_limit", v)
         return bool(v)
+
+    def set_wire_props(self, decode=False, egress=False):
+        """hb_set_wire_props: forwarded proposals on the wire path.  decode
+        (HB_WIRE_PROPS_IN): decode_follow() makes a batch record of a canonical forwarded
+        MsgProp, its entry run at eoff like a MsgApp's.  egress (HB_WIRE_PROPS_OUT): egress()
+        makes a split MsgProp record of every HB_EV_PROP_FWD event, hint = the proposal's
+        arrival index (etcd_amd.splice completes it with the entries the host holds)."""
+        bits = (abi.HB_WIRE_PROPS_IN if decode else 0) | (abi.HB_WIRE_PROPS_OUT if egress else 0)
+        _check("hb_set_wire_props", lib().hb_set_wire_props(self.h, bits))
+
+    def wire_props(self):
+        """hb_wire_props: the bits in force (HB_WIRE_PROPS_IN | HB_WIRE_PROPS_OUT)."""
+        v = lib().hb_wire_props(self.h)
+        if v < 0:
+            raise HipBatchError("hb_wire_props", v)
+        return v
 
     @staticmethod
     def _out_batch(out):

@@ -553,7 +553,8 @@ int  hb_decode(hb_handle* h, const uint8_t* bytes, const uint64_t* off, const ui
  *                            Data] ending at its span, with Type the one byte
  *                            00 or 01, Index == m.Index + 1 + k and len(Data)
  *                            <= HB_ENT_MAX_DATA: as above, plus its entry run
- * Any other record Unmarshal accepts stays HB_WIRE_HOST (MsgSnap, MsgProp, a
+ * Any other record Unmarshal accepts stays HB_WIRE_HOST (MsgSnap, MsgProp unless
+ * hb_set_wire_props has HB_WIRE_PROPS_IN on, a
  * MsgApp whose entries have another shape or whose Entry error the reference
  * drops).  The three response types give hb_decode's record with commit = 0.
  * info = type | slot << 4 | reject << 8; a MsgApp or MsgHeartbeat from a
@@ -673,6 +674,50 @@ int  hb_egress_caps(void);
 int  hb_set_egress_limit(hb_handle* h, int on);
 int  hb_egress_limit(hb_handle* h);
 int  hb_egress_limit_caps(void);         /* the cut features this library knows: HB_EGRESS_LIMIT_V1 */
+/* Forwarded proposals on the wire path (inside ABI 8, a
+ * knob of its own so that hb_decode_caps, hb_egress_caps and hb_egress_limit_caps
+ * keep their values).  With the bits at 0 (the default) every output of every
+ * call is what it was before the knob existed.
+ * HB_WIRE_PROPS_IN: hb_decode_follow makes an HB_WIRE_OK batch record of a
+ * MsgProp that is the message r.send forwards (raft/raft.go:616-624, :226-236)
+ * and nothing else:
+ *   - the canonical shape (as for a MsgApp with entries, above), Type MsgProp;
+ *   - Term == LogTerm == Index == Commit == 0, Reject false, RejectHint == 0;
+ *   - at least one entry (an empty MsgProp panics a leader: the host reports
+ *     it) and at most 2^23 - 1;
+ *   - every entry is 08 00 | 10 00 | 18 00 | [22 len Data] ending at its span:
+ *     Type, Term and Index the single byte 00 (what Propose makes; an
+ *     EntryConfChange goes to the host, which holds pendingConf), len(Data) <=
+ *     HB_ENT_MAX_DATA;
+ *   - group[i] < capacity.  m.From may be a non-member (slot HB_SLOT_NONE).
+ * Any other MsgProp stays HB_WIRE_HOST.  The batch record: info =
+ * HB_INFO(HB_MSG_PROP, slot, 0), term = 0, index = the entry count, hint =
+ * commit = 0; its entry run lies at eoff[i] like a MsgApp's, with eterm[k] = 0,
+ * edesc[k] = HB_ENT_DESC(len, 0, field 4 present), edata[k] = the offset of the
+ * first Data byte or 0.  eoff is one prefix sum over MsgApp and MsgProp runs;
+ * the entry total, the ent_cap rule and the sentinel are unchanged.  The fate
+ * of proposal i is in the step's events (HB_EV_LAST, HB_EV_PROP_FWD or
+ * HB_EV_PROP_DROP with x = i).
+ * HB_WIRE_PROPS_OUT: hb_egress makes one record per HB_EV_PROP_FWD event,
+ * placed by the event's position like every other record: info =
+ * HB_INFO(HB_MSG_PROP, to_ref, 0) | HB_OUT_ENTS with to_ref the event's lead ref
+ * (a slot, or HB_REF_OTHER), to = the slot's node id (0 for HB_REF_OTHER), term
+ * = log_term = index = commit = 0 (send leaves a MsgProp's Term at 0), hint =
+ * the event's x: the arrival index of the proposal in the stepped batch, or
+ * HB_NO_INDEX for a dense props[] proposal.  hb_encode writes it in the split
+ * form (status HB_WIRE_SPLICE | prefix_len) and the host completes it with the
+ * entries it holds for that arrival; hb_encode_ents never covers it.  No
+ * pre-step column is read and nothing is allocated: the next hb_egress or
+ * hb_decode_follow honours the bits.  The bit without egress on is legal and
+ * inert.  hb_set_wire_props waits for the handle's streams; HB_EINVAL for a NULL
+ * handle or any bit outside hb_wire_props_caps().  hb_wire_props returns the
+ * bits in force, HB_EINVAL for a NULL handle; a library that lacks
+ * hb_wire_props_caps lacks the knob. */
+#define HB_WIRE_PROPS_IN   1   /* hb_decode_follow: a canonical MsgProp becomes a batch record   */
+#define HB_WIRE_PROPS_OUT  2   /* hb_egress: HB_EV_PROP_FWD makes a MsgProp record               */
+int  hb_set_wire_props(hb_handle* h, int bits);
+int  hb_wire_props(hb_handle* h);
+int  hb_wire_props_caps(void);           /* HB_WIRE_PROPS_IN | HB_WIRE_PROPS_OUT */
 /* A vote record whose LogTerm the device cannot tell: info carries this flag
  * and log_term = 0; the host builds the message from its event as before.
  * Likewise a MsgApp record of append mode whose LogTerm, Commit or entry range
@@ -717,7 +762,8 @@ int  hb_egress_limit_caps(void);         /* the cut features this library knows:
  * the group appended a leader's entries or restored a snapshot earlier in the
  * same call until an HB_EV_COMMIT (Commit) and an HB_EV_TERM with a known
  * lastTerm (LogTerm) re-establish them.
- * Messages with a snapshot (HB_EV_SNAP) and HB_EV_PROP_FWD, without append mode
+ * Messages with a snapshot (HB_EV_SNAP), HB_EV_PROP_FWD unless hb_set_wire_props
+ * has HB_WIRE_PROPS_OUT on (then one MsgProp record each, see above), without append mode
  * HB_EV_APP and without vote mode HB_EV_VOTE, make no record: the host builds
  * them as before.  self_id is this node's id; a record holds no sender (hb_encode
  * writes m.From), so hb_egress only takes it for symmetry with hb_encode.
@@ -790,6 +836,8 @@ typedef struct hb_ent_source {       /* every pointer is device memory */
  * - A record that is not covered is written as hb_encode writes it: prefix ||
  *   suffix, status = HB_WIRE_SPLICE | prefix_len; the host completes that one.
  *   Coverage is decided per record: covered and uncovered records mix freely.
+ * - A record whose type is HB_MSG_PROP (hb_set_wire_props) is never covered: its
+ *   (index, hint] is (0, arrival index], not an index range of the group's log.
  * Sizes and offsets are 64-bit throughout: a record can be many megabytes and
  * the total can pass 2^32; there is no cap x 91 bound.  When *total > bytes_cap
  * no byte of `bytes` is written (off, status and total are): call again.

@@ -24,6 +24,13 @@ Workloads on a handle of 1,048,576 groups x 3:
           synth.window_sizes / attach_entry_descs make them, and each MsgApp
           with entries takes limitSize's cut from the group's size ring.
 
+  forward (--workload forward, a run of its own) a follower node's step of one
+          proposal per group (synth.follow_groups: every group has a lead), mode 1: every
+          group's HB_EV_PROP_FWD word.  hb_egress + hb_encode over that one step's events with
+          hb_set_wire_props(HB_WIRE_PROPS_OUT) off (no record: the host replays the events and
+          marshals every MsgProp) and on (one split MsgProp record per group), interleaved
+          repetition by repetition.
+
 Per workload: the step (or tick) runs once with egress on, then hb_egress +
 hb_encode (chained through the device-resident count, no host sync between
 them) run 3 warm-up and 25 timed times over that step's events, each pair
@@ -44,6 +51,7 @@ back-to-back steps of the follow and the cfg2 workload with egress off, on
   python tools/microbench/egress_bench.py --workload campaign [--out profiles/egress_vote_bench.json]
   python tools/microbench/egress_bench.py --workload cfg2 [--out profiles/egress_app_bench.json]
   python tools/microbench/egress_bench.py --workload cfg2 --max-msg-size 1048576
+  python tools/microbench/egress_bench.py --workload forward [--out profiles/wire_props_forward.json]
 """
 import argparse
 import json
@@ -230,21 +238,66 @@ def cfg2_main(args, torch, stream):
     return dict(bench="hb_egress + hb_encode, append mode", results=results, snapshot_cost=snapshot)
 
 
+def forward_main(args, torch, stream):
+    seed = 0x5EED0006
+    g, _ = synth.follow_groups(G, N, seed=seed, with_runs=False)
+    eng = Engine(G, max_replicas=N, max_inflight=W, max_batch=G, stream=stream)
+    eng.load_groups(g)
+    eng.load_peers(peers())
+    eng.set_egress(True)
+    grp = np.random.default_rng(seed).permutation(G).astype(np.uint32)
+    d = dict(group=dv(torch, grp), info=dv(torch, np.full(G, abi.hb_info(abi.HB_MSG_PROP, 0), np.uint32)),
+             zero=dv(torch, np.zeros(G, np.uint64)), one=dv(torch, np.ones(G, np.uint64)))
+    eng.step(d["group"], d["info"], d["zero"], d["one"], d["zero"], None, host=False, msg_props=True)
+    sink = Sink(torch, G)
+    us = {False: [], True: []}
+    for rep in range(3 + args.reps):
+        for on in (False, True):
+            eng.set_wire_props(egress=on)  # (waits for the stream; the step's events stay good)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            sink.run(eng)
+            e1.record(stream)
+            e1.synchronize()
+            if rep >= 3:
+                us[on].append(e0.elapsed_time(e1) * 1e3)
+    results = []
+    for on in (False, True):
+        eng.set_wire_props(egress=on)
+        sink.run(eng)
+        eng.sync()
+        r = report(f"forward: one proposal per group at a follower, wire_props egress {'on' if on else 'off'}", eng, sink,
+                   us[on], args.reps)
+        n = r["records"]
+        assert n == (G if on else 0)
+        if on:
+            info = sink.out["info"].cpu().numpy().view(np.uint32)
+            status = sink.status.cpu().numpy()
+            assert (info == (abi.hb_info(abi.HB_MSG_PROP, 1) | abi.HB_OUT_ENTS)).all()
+            assert (status & abi.HB_WIRE_SPLICE != 0).all()
+            hint = np.sort(sink.out["hint"].cpu().numpy().view(np.uint64))
+            assert np.array_equal(hint, np.arange(G, dtype=np.uint64))
+        r["wire_props_egress"] = on
+        results.append(r)
+    eng.close()
+    return dict(bench="hb_egress + hb_encode, forwarded proposals", results=results)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--workload", choices=("egress", "campaign", "cfg2"), default="egress")
+    ap.add_argument("--workload", choices=("egress", "campaign", "cfg2", "forward"), default="egress")
     ap.add_argument("--max-msg-size", type=int, default=0,
                     help="cfg2 only: a finite MaxSizePerMsg, with hb_set_egress_limit on (0: no limit, the default)")
     args = ap.parse_args()
     import torch
     stream = torch.cuda.Stream()
     results, snapshot = [], []
-    if args.workload == "cfg2":
+    if args.workload in ("cfg2", "forward"):
         with torch.cuda.stream(stream):
-            out = cfg2_main(args, torch, stream)
+            out = (cfg2_main if args.workload == "cfg2" else forward_main)(args, torch, stream)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:

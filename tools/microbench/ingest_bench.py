@@ -21,6 +21,14 @@ per entry (eterm, edesc, edata) + 8 B eoff.  (The model counts the record bytes 
 the second walk reads the records with entries again.)
 
   python tools/microbench/ingest_bench.py [--out profiles/ingest_bench.json]
+
+--workload prop: a step's worth of forwarded proposals on a handle that leads
+1,048,576 groups x 3, one MsgProp per group with one entry of 16 B and of 1 KiB Data, through
+hb_decode_follow with hb_set_wire_props(HB_WIRE_PROPS_IN) (every record an HB_WIRE_OK batch
+record with its entry run) beside the same bytes through hb_decode (every record
+HB_WIRE_HOST: what the host unmarshals today), interleaved repetition by repetition.  The byte
+model is the one above; the payload bytes are counted, though the parser reads only the
+window lines that hold them.
 """
 import argparse
 import json
@@ -106,6 +114,83 @@ def self_check(b, data, off, ln, k=512):
         assert data[int(off[i]):int(off[i]) + int(ln[i])].tobytes() == want, i
 
 
+def encode_props(G, data_len, to=1, frm=2):
+    """One forwarded MsgProp per group as Message.MarshalTo writes it: one entry of data_len bytes."""
+    from etcd_amd.splice import varint
+    ent = bytes([0x08, 0, 0x10, 0, 0x18, 0, 0x22]) + varint(data_len)
+    head = bytes([0x08, abi.HB_MSG_PROP, 0x10, to, 0x18, frm, 0x20, 0, 0x28, 0, 0x30, 0, 0x3A]) + \
+        varint(len(ent) + data_len) + ent
+    tail = bytes([0x40, 0]) + SNAP + bytes([0x50, 0, 0x58, 0])
+    L = len(head) + data_len + len(tail)
+    out = np.zeros((G, L), np.uint8)
+    out[:, :len(head)] = np.frombuffer(head, np.uint8)
+    out[:, len(head):len(head) + data_len] = (np.arange(G)[:, None] + np.arange(data_len)[None, :]) & 0xFF
+    out[:, len(head) + data_len:] = np.frombuffer(tail, np.uint8)
+    return out.reshape(-1), np.arange(G, dtype=np.uint64) * np.uint64(L), np.full(G, L, np.uint32), len(head)
+
+
+def main_prop(args):
+    import torch
+    from tests.wire_util import gogo_marshal
+    G = args.groups
+    stream = torch.cuda.Stream()
+    g, _ = synth.steady_groups(G, N, seed=0x5EED0002, with_runs=False)
+    eng = Engine(G, max_replicas=N, max_inflight=W, max_batch=G + 1, stream=stream)
+    eng.load_groups(g)
+    peers = np.zeros((G, abi.HB_MAX_REPLICAS), np.uint64)
+    peers[:, :N] = np.arange(1, N + 1, dtype=np.uint64)
+    eng.load_peers(peers)
+    eng.set_wire_props(decode=True)
+    grp = np.arange(G, dtype=np.uint32)
+    res = []
+    for data_len in (16, 1024):
+        data, off, ln, at = encode_props(G, data_len)
+        for i in (0, 1, G - 1):
+            want = gogo_marshal(abi.HB_MSG_PROP, to=1, frm=2, entries=[(0, 0, 0, bytes((i + j) & 0xFF for j in range(data_len)))])
+            assert data[int(off[i]):int(off[i]) + int(ln[i])].tobytes() == want, i
+        ent_cap = G
+        with torch.cuda.stream(stream):
+            d = [dv(torch, x) for x in (data, off, ln, grp)]
+            z = lambda k, dt: torch.zeros(max(k, 1), dtype=dt, device="cuda")  # noqa: E731
+            out = dict(group=z(G + 1, torch.int32), info=z(G + 1, torch.int32), term=z(G + 1, torch.int64),
+                       index=z(G + 1, torch.int64), hint=z(G + 1, torch.int64), commit=z(G + 1, torch.int64),
+                       eoff=z(G + 1, torch.int64), eterm=z(ent_cap, torch.int64), edesc=z(ent_cap, torch.int32))
+            edata, n_ent, status, hstatus = z(ent_cap, torch.int64), z(1, torch.int64), z(G, torch.uint8), z(G, torch.uint8)
+        torch.cuda.synchronize()
+        fns = (("decode_follow props", lambda: eng.decode_follow(d[0], d[1], d[2], d[3], out, status, ent_cap, edata, n_ent)),
+               ("decode (host's today)", lambda: eng.decode(d[0], d[1], d[2], d[3], out, hstatus)))
+        us = {name: [] for name, _ in fns}
+        for rep in range(3 + args.reps):
+            for name, fn in fns:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                fn()
+                e1.record(stream)
+                e1.synchronize()
+                if rep >= 3:
+                    us[name].append(e0.elapsed_time(e1) * 1e3)
+        eng.decode_follow(d[0], d[1], d[2], d[3], out, status, ent_cap, edata, n_ent)
+        eng.sync()
+        assert int(n_ent.item()) == G and bool((status == abi.HB_WIRE_OK).all().item())
+        assert bool((hstatus == abi.HB_WIRE_HOST).all().item())
+        assert bool((edata == torch.from_numpy((off + np.uint64(at)).view(np.int64)).cuda()).all().item())
+        for name, model in (("decode_follow props", len(data) + G * (16 + 64 + 48 + 1 + 8 + 20)),
+                            ("decode (host's today)", len(data) + G * (16 + 64 + 32 + 1))):
+            r = dict(case=name, workload="prop", data_len=data_len, groups=G, replicas=N, reps=args.reps, records=G,
+                     wire_bytes=int(len(data)), entries=G if "props" in name else 0, event_us=stat(us[name]),
+                     model_bytes=int(model))
+            med = r["event_us"]["median"]
+            r.update(model_GBps_at_median=float(model / med / 1e3), ns_per_record_at_median=float(med * 1e3 / G))
+            print(json.dumps(r), flush=True)
+            res.append(r)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    eng.close()
+
+
 def stat(us):
     return dict(median=float(np.median(us)), min=float(np.min(us)), max=float(np.max(us)))
 
@@ -115,7 +200,10 @@ def main():
     ap.add_argument("--groups", type=int, default=1 << 20)
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--workload", choices=("follow", "prop"), default="follow")
     args = ap.parse_args()
+    if args.workload == "prop":
+        return main_prop(args)
     import torch
     G = args.groups
     stream = torch.cuda.Stream()
