@@ -116,6 +116,7 @@ HB_DECODE_FOLLOW = 1      # hb_decode_caps bit: hb_decode_follow
 HB_ENCODE_ENTS = 1        # hb_encode_caps bit: hb_encode_ents
 HB_FRAME_V1 = 1           # hb_frame_caps bit: hb_frame / hb_unframe / hb_gid_dir_build
 HB_EGRESS_LIMIT_V1 = 1    # hb_egress_limit_caps bit: hb_set_egress_limit / hb_egress_limit
+HB_EGRESS_LOGTERM_V1 = 1  # hb_egress_logterm_caps bit: hb_set_egress_logterm / hb_egress_logterm
 HB_WIRE_PROPS_IN = 1      # hb_set_wire_props bit: hb_decode_follow takes a canonical forwarded MsgProp
 HB_WIRE_PROPS_OUT = 2     # hb_set_wire_props bit: hb_egress makes a MsgProp record of HB_EV_PROP_FWD
 # hb_unframe's fstatus

@@ -4394,6 +4394,7 @@ struct EgressArgs {
   const uint64_t *commit0, *bl0, *blt0;
   uint64_t max_msg_size;
   const uint64_t *szx, *szlo;  // CUT only (else null): the groups' size rings as they stand at hb_egress
+  const uint64_t *trx, *trc;   // LT only (else null): the groups' older-runs rings as they stand at hb_egress
   uint32_t* ccnt;    // [nc] records per chunk
   uint64_t* cbase;   // [nc + 1] their exclusive scan, then the total
   uint64_t cap;
@@ -4484,9 +4485,14 @@ __global__ void __launch_bounds__(1024) k_eg_small(EgressArgs a) {
 // unless the ring no longer holds cum(x) or the group has a follower append / restore anywhere in
 // the call's events.  The record count of a word does not depend on it, so the count kernels do
 // not take the parameter.
-template <bool VOTES, bool APPS, bool CUT, bool FWD>
+// LT (hb_set_egress_logterm on an append-mode handle): an aux = 0 MsgApp that is
+// not at the boundary takes its LogTerm from the group's older-runs ring instead of the flag,
+// unless the ring no longer reaches down to its Index or the group has a follower append / restore
+// anywhere in the call's events (the same look-ahead as CUT's, made once for both).
+template <bool VOTES, bool APPS, bool CUT, bool FWD, bool LT>
 __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
   static_assert(APPS || !CUT, "the cut is a MsgApp's");
+  static_assert(APPS || !LT, "the LogTerm lookup is a MsgApp's");
   __shared__ uint64_t s_w[EG_TILE];
   __shared__ uint32_t s_pos[EG_TILE];
   __shared__ uint4 s_key[EG_TILE / 16];
@@ -4497,11 +4503,18 @@ __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
   // wave's sends one lane at a time, and a load there would be waited for at every visit.  The
   // extent word is 0 where the ring cannot be trusted (rule (ii): the in-order replay has no
   // look-ahead, so the partition's words are read once before it; a plain same-value byte store)
-  uint64_t sx = 0, slo = 0;
-  if (CUT) {
-    if (live) {
+  // LT: likewise the two words of the group's older-runs ring; the count word is 0 (no run: every
+  // lookup fails, rule (i)) where rule (ii) holds.  Only the search itself, dependent loads from
+  // the ring, stands in the send's rare sub-branch.
+  uint64_t sx = 0, slo = 0, tx = 0, tc = 0;
+  if (CUT || LT) {
+    if (CUT && live) {
       sx = a.szx[g];
       slo = a.szlo[g];
+    }
+    if (LT && live) {
+      tx = a.trx[g];
+      tc = a.trc[g];
     }
     __shared__ uint8_t s_fol[256];  // by a word's group byte
     static_assert(PART <= 256, "a word's group byte names a lane of the partition");
@@ -4519,7 +4532,10 @@ __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
       }
     }
     __syncthreads();
-    if (s_fol[tid] != 0) sx = 0;
+    if (s_fol[tid] != 0) {
+      if (CUT) sx = 0;
+      if (LT) tc = 0;
+    }
   }
   uint64_t term = live ? a.term0[g] : 0ull, last = live ? a.last0[g] : 0ull;
   uint64_t lt = 0;  // VOTES: raftLog.lastTerm() at this point of the replay, or HB_LT_UNKNOWN
@@ -4628,8 +4644,18 @@ __global__ void __launch_bounds__(PART) k_egress(EgressArgs a) {
               // LogTerm: the Term when the aux bit says so, the boundary's term for a send at the
               // boundary; anything the replay cannot prove leaves the record to the host.
               const bool at_bl = bl != HB_NO_INDEX && xv == bl && blt != HB_LT_UNKNOWN;
-              bool host = !((aux & 1u) || at_bl) || !cm_known;
-              const uint64_t lterm = (aux & 1u) ? term : blt;
+              bool lt_known = (aux & 1u) || at_bl;
+              uint64_t lterm = (aux & 1u) ? term : blt;
+              if (LT && !lt_known) {  // below the boundary: Runs::find over the ring as it stands now
+                Runs r;
+                r.R = lx_base(tx);
+                r.mask = lx_cap(tx) - 1;
+                r.n = (uint32_t)tc;
+                r.h = (uint32_t)(tc >> 32);
+                lt_known = true;
+                lterm = r.find(xv, &lt_known);
+              }
+              bool host = !lt_known || !cm_known;
               const bool ents = xv < last;  // entries (x, L]
               uint64_t L = 0;
               if (ents) {
@@ -5739,6 +5765,7 @@ struct hb_handle {
   bool egress = false;
   bool eg_stepped = false;        // a step or tick has run since hb_set_egress(on)
   bool eg_limit = false;          // hb_set_egress_limit: limitSize's cut at hb_egress (§3.23)
+  bool eg_logterm = false;        // hb_set_egress_logterm: a resend's LogTerm from the run ring (§3.25)
   int wire_props = 0;             // hb_set_wire_props: HB_WIRE_PROPS_IN | HB_WIRE_PROPS_OUT (§3.24)
   bool eg_votes = false;          // HB_EGRESS_VOTES: MsgVote records, the lterm0 column
   Dev<uint64_t> lterm0;           // [G] raftLog.lastTerm() before the last step / tick, or HB_LT_UNKNOWN
@@ -7239,6 +7266,23 @@ int hb_egress_limit(hb_handle* h) { return h ? (h->eg_limit ? 1 : 0) : HB_EINVAL
 
 int hb_egress_limit_caps(void) { return HB_EGRESS_LIMIT_V1; }
 
+int hb_set_egress_logterm(hb_handle* h, int on) {
+  if (!h) return HB_EINVAL;
+  const bool want = on != 0;
+  if (want == h->eg_logterm) return HB_OK;
+  if (h->egress) {  // as hb_set_egress_limit: a mode change
+    DeviceGuard guard(h->device);
+    HB_CHECK(hipStreamSynchronize(h->stream));
+    h->eg_stepped = false;
+  }
+  h->eg_logterm = want;
+  return HB_OK;
+}
+
+int hb_egress_logterm(hb_handle* h) { return h ? (h->eg_logterm ? 1 : 0) : HB_EINVAL; }
+
+int hb_egress_logterm_caps(void) { return HB_EGRESS_LOGTERM_V1; }
+
 int hb_set_wire_props(hb_handle* h, int bits) {
   if (!h || (bits & ~(HB_WIRE_PROPS_IN | HB_WIRE_PROPS_OUT)) != 0) return HB_EINVAL;
   if (bits == h->wire_props) return HB_OK;
@@ -7286,6 +7330,9 @@ int hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t 
   const bool cut = h->eg_limit && h->eg_apps && sz_on(h->max_msg_size);
   ea.szx = cut ? h->st.szx : nullptr;
   ea.szlo = cut ? h->st.szlo : nullptr;
+  const bool lt = h->eg_logterm && h->eg_apps;
+  ea.trx = lt ? h->st.trx : nullptr;
+  ea.trc = lt ? h->st.trc : nullptr;
   ea.ccnt = h->eg_cnt.get();
   ea.cbase = h->eg_base.get();
   ea.cap = cap;
@@ -7303,21 +7350,33 @@ int hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t 
   // (a word's record count does not depend on the cut: the count kernels are append mode's)
   // (with HB_WIRE_PROPS_OUT off the instantiations are the ones a handle without the knob ran)
   const bool fwd = (h->wire_props & HB_WIRE_PROPS_OUT) != 0;
-#define EG_LAUNCH_F(V, A, C, F)                                                                      \
+#define EG_LAUNCH_F(V, A, C, F, L)                                                                    \
   do {                                                                                               \
     if (small) hipLaunchKernelGGL((k_eg_small<V, A, F>), dim3(1), dim3(1024), 0, h->stream, ea);    \
     else {                                                                                           \
       hipLaunchKernelGGL((k_eg_count<V, A, F>), dim3(ea.nc), dim3(256), 0, h->stream, ea);          \
       hipLaunchKernelGGL(k_eg_scan, dim3(1), dim3(1024), 0, h->stream, ea);                         \
     }                                                                                                \
-    hipLaunchKernelGGL((k_egress<V, A, C, F>), dim3(h->NB), dim3(PART), 0, h->stream, ea);          \
+    hipLaunchKernelGGL((k_egress<V, A, C, F, L>), dim3(h->NB), dim3(PART), 0, h->stream, ea);       \
   } while (0)
-#define EG_LAUNCH(V, A, C)                 \
-  do {                                     \
-    if (fwd) EG_LAUNCH_F(V, A, C, true);   \
-    else EG_LAUNCH_F(V, A, C, false);      \
+#define EG_LAUNCH(V, A, C)                        \
+  do {                                            \
+    if (fwd) EG_LAUNCH_F(V, A, C, true, false);   \
+    else EG_LAUNCH_F(V, A, C, false, false);      \
   } while (0)
-  if (cut) {
+  // (the lookup's instantiations exist for append mode only; with the knob off the ones above run)
+#define EG_LAUNCH_LT(V, C)                          \
+  do {                                              \
+    if (fwd) EG_LAUNCH_F(V, true, C, true, true);   \
+    else EG_LAUNCH_F(V, true, C, false, true);      \
+  } while (0)
+  if (lt) {
+    if (cut) {
+      if (h->eg_votes) EG_LAUNCH_LT(true, true);
+      else EG_LAUNCH_LT(false, true);
+    } else if (h->eg_votes) EG_LAUNCH_LT(true, false);
+    else EG_LAUNCH_LT(false, false);
+  } else if (cut) {
     if (h->eg_votes) EG_LAUNCH(true, true, true);
     else EG_LAUNCH(false, true, true);
   } else if (h->eg_apps) {
@@ -7325,6 +7384,7 @@ int hb_egress(hb_handle* h, uint64_t self_id, const hb_out_batch* out, uint64_t 
     else EG_LAUNCH(false, true, false);
   } else if (h->eg_votes) EG_LAUNCH(true, false, false);
   else EG_LAUNCH(false, false, false);
+#undef EG_LAUNCH_LT
 #undef EG_LAUNCH
 #undef EG_LAUNCH_F
   return hipGetLastError() == hipSuccess ? HB_OK : HB_EDEVICE;

@@ -130,6 +130,9 @@ def lib():
         "hb_set_egress_limit": (C.c_int, [H, C.c_int]),
         "hb_egress_limit": (C.c_int, [H]),
         "hb_egress_limit_caps": (C.c_int, []),
+        "hb_set_egress_logterm": (C.c_int, [H, C.c_int]),
+        "hb_egress_logterm": (C.c_int, [H]),
+        "hb_egress_logterm_caps": (C.c_int, []),
         "hb_set_wire_props": (C.c_int, [H, C.c_int]),
         "hb_wire_props": (C.c_int, [H]),
         "hb_wire_props_caps": (C.c_int, []),
@@ -468,6 +471,20 @@ class Engine:
         v = lib().hb_egress_limit(self.h)
         if v < 0:
             raise HipBatchError("hb_egress_limit", v)
+        return bool(v)
+
+    def set_egress_logterm(self, on=True):
+        """hb_set_egress_logterm: in append mode, a MsgApp record whose send lies below the
+        leader's boundary carries the term of its Index, read from the group's older-runs ring
+        where the device can prove it, instead of HB_OUT_HOST.  egress() then runs before any
+        call that rewrites a group's run ring (load_term_runs, load / remove / move groups)."""
+        _check("hb_set_egress_logterm", lib().hb_set_egress_logterm(self.h, 1 if on else 0))
+
+    def egress_logterm(self):
+        """hb_egress_logterm: whether the knob is on."""
+        v = lib().hb_egress_logterm(self.h)
+        if v < 0:
+            raise HipBatchError("hb_egress_logterm", v)
         return bool(v)
 
     def set_wire_props(self, decode=False, egress=False):

@@ -674,6 +674,34 @@ int  hb_egress_caps(void);
 int  hb_set_egress_limit(hb_handle* h, int on);
 int  hb_egress_limit(hb_handle* h);
 int  hb_egress_limit_caps(void);         /* the cut features this library knows: HB_EGRESS_LIMIT_V1 */
+/* A probe resend's LogTerm in append mode (inside ABI 8,
+ * a knob of its own like hb_set_egress_limit).  Off (the default): a MsgApp
+ * record whose send lies below the index just under the leader's current-term
+ * run is HB_OUT_HOST, and every output of every call is what it was before the
+ * knob existed.  On, on a handle in append mode: such a record carries
+ * log_term = the term of `index`, read at hb_egress from the group's ring of
+ * older term runs (hb_load_term_runs and what the engine pushed since), as
+ * raftLog.term gives it (raft/raft.go:261-281).  The record stays HB_OUT_HOST
+ * where that read cannot be proven to be the send's: (i) the ring's oldest run
+ * starts above `index` (the runs were never loaded that far, or Term changes
+ * later in the call pushed that run out of a full ring); (ii) the group has a
+ * follower append or restore (HB_EV_FOLLOW with aux APPEND / RESTORE) anywhere
+ * in the same call, before or after the send, which may have cut the ring.
+ * The other reasons to flag a record (Commit unknown, the limit without
+ * hb_set_egress_limit) and every other column are unchanged, and a send at the
+ * boundary keeps the boundary's term without a read; without append mode the
+ * knob changes nothing.  Precondition while on: hb_egress runs before any call
+ * that rewrites a group's run ring (hb_load_term_runs, hb_load_groups,
+ * hb_remove_groups, hb_move_groups), as it already runs before the next step;
+ * hb_reserve_log keeps the runs in order and hb_set_log_bounds does not touch
+ * them, so both may come first.  A change of the knob while egress is on waits
+ * for the stream, and hb_egress gives count 0 until the next step or tick, as
+ * a mode change does.  hb_egress_logterm returns 0 or 1, HB_EINVAL for a NULL
+ * handle; a library that lacks hb_egress_logterm_caps lacks the knob. */
+#define HB_EGRESS_LOGTERM_V1 1
+int  hb_set_egress_logterm(hb_handle* h, int on);
+int  hb_egress_logterm(hb_handle* h);
+int  hb_egress_logterm_caps(void);       /* the lookup features this library knows: HB_EGRESS_LOGTERM_V1 */
 /* Forwarded proposals on the wire path (inside ABI 8, a
  * knob of its own so that hb_decode_caps, hb_egress_caps and hb_egress_limit_caps
  * keep their values).  With the bits at 0 (the default) every output of every

@@ -31,6 +31,15 @@ Workloads on a handle of 1,048,576 groups x 3:
           marshals every MsgProp) and on (one split MsgProp record per group), interleaved
           repetition by repetition.
 
+  catchup (--workload catchup, a run of its own) the catch-up after an election:
+          every group a leader whose follower 2 is in Probe at the boundary (Next = the first
+          index of the current-term run) and rejects that probe with a hint two entries lower,
+          so the step resends below the boundary: one MsgApp per group whose LogTerm is in no
+          event.  --logterm 0: every record is HB_OUT_HOST; --logterm 1
+          (hb_set_egress_logterm): every record carries the term read from the group's run
+          ring.  One knob value per process, so that the two can be interleaved process by
+          process; --workload cfg2 takes --logterm too (no send there is below the boundary).
+
 Per workload: the step (or tick) runs once with egress on, then hb_egress +
 hb_encode (chained through the device-resident count, no host sync between
 them) run 3 warm-up and 25 timed times over that step's events, each pair
@@ -52,6 +61,7 @@ back-to-back steps of the follow and the cfg2 workload with egress off, on
   python tools/microbench/egress_bench.py --workload cfg2 [--out profiles/egress_app_bench.json]
   python tools/microbench/egress_bench.py --workload cfg2 --max-msg-size 1048576
   python tools/microbench/egress_bench.py --workload forward [--out profiles/wire_props_forward.json]
+  python tools/microbench/egress_bench.py --workload catchup --logterm 1
 """
 import argparse
 import json
@@ -212,6 +222,7 @@ def cfg2_main(args, torch, stream):
         bd = synth.attach_entry_descs(b0, G, seed=seed + 2)
         sized = {k: dv(torch, bd[k]) for k in ("edesc", "eoff", "peoff")}
         eng.set_egress_limit(True)
+    eng.set_egress_logterm(bool(args.logterm))
 
     def cfg2(k):
         eng.step(x["group"], x["info"], x["term"], x["index"] + k, None, x["props"], host=False, **sized)
@@ -233,9 +244,60 @@ def cfg2_main(args, torch, stream):
     assert r["records_spliced"] == r["records_entries_flag"] == 2 * G and r["records_flagged"] == 0
     assert (status[info & abi.HB_OUT_ENTS == 0] == abi.HB_WIRE_OK).all()
     r["max_msg_size"] = limit
+    r["logterm"] = bool(args.logterm)
     results.append(r)
     eng.close()
     return dict(bench="hb_egress + hb_encode, append mode", results=results, snapshot_cost=snapshot)
+
+
+def catchup_main(args, torch, stream):
+    seed = 0x5EED0025
+    g, _ = synth.steady_groups(G, N, seed=seed, with_runs=False)
+    # the current-term run starts at 4 or later, the Term is 2 or more: the index two below the
+    # boundary exists and lies in the older run (0, Term - 1) that load_one_older_run loads
+    tf = np.maximum(g["term_first"], 4).astype(np.uint64)
+    last = np.maximum(g["last_index"], tf).astype(np.uint64)
+    g["term"] = np.maximum(g["term"], 2)
+    g["term_first"] = tf
+    for f in ("last_index", "committed", "term_last"):
+        g[f] = last
+    pr = g["pr"]
+    for s in range(N):
+        pr[:, s]["match"] = last
+        pr[:, s]["next"] = last + np.uint64(1)
+    pr[:, 1]["state"], pr[:, 1]["match"], pr[:, 1]["next"] = abi.HB_PR_PROBE, 0, tf
+    eng = Engine(G, max_replicas=N, max_inflight=W, max_batch=G, stream=stream)
+    eng.load_groups(g)
+    eng.load_peers(peers())
+    load_one_older_run(eng, g)
+    eng.set_egress(True, apps=True)
+    eng.set_egress_logterm(bool(args.logterm))
+    grp = np.random.default_rng(seed).permutation(G).astype(np.uint32)
+    rej = abi.hb_info(abi.HB_MSG_APP_RESP, 1) | (1 << 8)
+    d = dict(group=dv(torch, grp), info=dv(torch, np.full(G, rej, np.uint32)), term=dv(torch, g["term"][grp]),
+             index=dv(torch, tf[grp] - np.uint64(1)), hint=dv(torch, tf[grp] - np.uint64(3)))
+    eng.step(d["group"], d["info"], d["term"], d["index"], d["hint"], None, host=False)
+    sink = Sink(torch, G)
+    us = timed(torch, stream, eng, sink, args.reps)
+    r = report(f"catchup: one resend two below the boundary per group, logterm {'on' if args.logterm else 'off'}", eng,
+               sink, us, args.reps, snap=48)
+    info = sink.out["info"].cpu().numpy().view(np.uint32)
+    status = sink.status.cpu().numpy()
+    r["records_flagged"] = int((info & abi.HB_OUT_HOST != 0).sum())
+    r["records_spliced"] = int((status & abi.HB_WIRE_SPLICE != 0).sum())
+    r["logterm"] = bool(args.logterm)
+    assert r["records"] == G and ((info & 0xF) == abi.HB_MSG_APP).all()
+    order = sink.out["group"].cpu().numpy().view(np.uint32)
+    assert np.array_equal(sink.out["index"].cpu().numpy().view(np.uint64), tf[order] - np.uint64(3))
+    if args.logterm:
+        assert r["records_flagged"] == 0 and r["records_spliced"] == G
+        assert np.array_equal(sink.out["log_term"].cpu().numpy().view(np.uint64), g["term"][order] - np.uint64(1))
+        assert np.array_equal(sink.out["hint"].cpu().numpy().view(np.uint64), last[order])
+    else:
+        assert r["records_flagged"] == G and r["wire_bytes"] == 0
+    print(json.dumps({k: r[k] for k in ("records", "records_spliced", "records_flagged")}), flush=True)
+    eng.close()
+    return dict(bench="hb_egress + hb_encode, catch-up below the boundary", results=[r])
 
 
 def forward_main(args, torch, stream):
@@ -288,16 +350,18 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=25)
     ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--workload", choices=("egress", "campaign", "cfg2", "forward"), default="egress")
+    ap.add_argument("--workload", choices=("egress", "campaign", "cfg2", "forward", "catchup"), default="egress")
     ap.add_argument("--max-msg-size", type=int, default=0,
                     help="cfg2 only: a finite MaxSizePerMsg, with hb_set_egress_limit on (0: no limit, the default)")
+    ap.add_argument("--logterm", type=int, choices=(0, 1), default=0,
+                    help="cfg2 and catchup: hb_set_egress_logterm on (DESIGN.md 3.25; 0: off, the default)")
     args = ap.parse_args()
     import torch
     stream = torch.cuda.Stream()
     results, snapshot = [], []
-    if args.workload in ("cfg2", "forward"):
+    if args.workload in ("cfg2", "forward", "catchup"):
         with torch.cuda.stream(stream):
-            out = (cfg2_main if args.workload == "cfg2" else forward_main)(args, torch, stream)
+            out = dict(cfg2=cfg2_main, forward=forward_main, catchup=catchup_main)[args.workload](args, torch, stream)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:
