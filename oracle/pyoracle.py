@@ -280,9 +280,11 @@ class Progress:
 
 
 def Msg(Type, From=0, To=0, Term=0, Index=0, LogTerm=0, Commit=0, Reject=False, RejectHint=0, Entries=0,
-        Snapshot=None):
+        Snapshot=None, edesc=None):
     """pb.Message for the oracle.  Entries: a count (MsgProp) or a list of
-    (index, term) pairs (MsgApp; indices must follow Index); Snapshot: (index, term)."""
+    (index, term) pairs (MsgApp; indices must follow Index); Snapshot: (index, term);
+    edesc: one HB_ENT_DESC per entry (a finite max_msg_size needs Entry.Size(); None:
+    every entry is pb.Entry{} with its Term and Index)."""
     m = orc_msg()
     m.Type, m.From, m.To, m.Term, m.Index = Type, From, To, Term, Index
     m.LogTerm, m.Commit, m.Reject, m.RejectHint = LogTerm, Commit, int(Reject), RejectHint
@@ -294,6 +296,10 @@ def Msg(Type, From=0, To=0, Term=0, Index=0, LogTerm=0, Commit=0, Reject=False, 
         m.nents = len(Entries)
     else:
         m.nents = Entries
+    if edesc is not None:
+        assert len(edesc) == m.nents, "one descriptor per entry"
+        m._descs = (C.c_uint32 * max(1, len(edesc)))(*edesc)  # kept alive with m
+        m.edesc = C.cast(m._descs, C.c_void_p)
     if Snapshot is not None:
         m.snap_index, m.snap_term = Snapshot
     return m

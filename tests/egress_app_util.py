@@ -53,8 +53,7 @@ def replay_apps(events, groups0, runs, peers, self_id, max_msg_size=abi.HB_NO_LI
     tuples of APP_FIELDS in event order; votes=False leaves the MsgVote records out (mode 5)."""
     state = {}
     out = []
-    for e in events:
-        g = int(e["group"])
+    for x, g, t, to, aux in np.asarray(events).tolist():  # (abi.EVENT_DTYPE's field order)
         s = state.get(g)
         if s is None:
             rr = runs.get(g) if isinstance(runs, dict) else runs[g]
@@ -64,7 +63,6 @@ def replay_apps(events, groups0, runs, peers, self_id, max_msg_size=abi.HB_NO_LI
                                 blt=blt)
         if s["dead"]:  # faulted: the replay ended
             continue
-        t, to, aux, x = int(e["type"]), int(e["to"]), int(e["aux"]), int(e["x"])
         if t == abi.HB_EV_TERM:
             s["term"] = x
             s["bl"], s["blt"] = (UNKNOWN if s["pend"] else s["last"]), s["lt"]

@@ -22,6 +22,8 @@ group up to its first follower append / restore, where rule (ii) takes over.
 tests/test_egress_logterm_replay.py pins the rules to the oracle's own r.msgs;
 tests/test_egress_logterm_gpu.py uses them as the device's reference.
 """
+import numpy as np
+
 from etcd_amd import abi
 
 from .egress_app_util import boundary, is_app, replay_apps
@@ -71,8 +73,7 @@ def lookup_sends(events, groups0, runs):
     """Per HB_EV_APP event, in event order: whether the send is one the lookup is for (aux = 0 and
     not at the known boundary), by the boundary rules of egress_app_util.replay_apps."""
     state, out = {}, []
-    for e in events:
-        g = int(e["group"])
+    for x, g, t, _, aux in np.asarray(events).tolist():  # (abi.EVENT_DTYPE's field order)
         s = state.get(g)
         if s is None:
             rr = runs.get(g) if isinstance(runs, dict) else runs[g]
@@ -81,7 +82,6 @@ def lookup_sends(events, groups0, runs):
                                 lt=last_term(groups0[g], rr), bl=bl, blt=blt)
         if s["dead"]:
             continue
-        t, aux, x = int(e["type"]), int(e["aux"]), int(e["x"])
         if t == abi.HB_EV_TERM:
             s["term"] = x
             s["bl"], s["blt"] = (UNKNOWN if s["pend"] else s["last"]), s["lt"]

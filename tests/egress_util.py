@@ -22,14 +22,12 @@ def replay(events, groups0, peers, self_id):
     tuples of FIELDS, in event order."""
     state = {}
     out = []
-    for e in events:
-        g = int(e["group"])
+    for x, g, t, to, aux in np.asarray(events).tolist():  # (abi.EVENT_DTYPE's field order)
         s = state.get(g)
         if s is None:
             s = state[g] = [int(groups0[g]["term"]), int(groups0[g]["last_index"]), False, False]
         if s[3]:  # faulted: the replay ended
             continue
-        t, to, aux, x = int(e["type"]), int(e["to"]), int(e["aux"]), int(e["x"])
         if t == abi.HB_EV_TERM:
             s[0] = x
         elif t == abi.HB_EV_LAST:

@@ -57,8 +57,7 @@ def replay_votes(events, groups0, runs, peers, self_id):
     (last_term).  Returns tuples of VOTE_FIELDS in event order."""
     state = {}
     out = []
-    for e in events:
-        g = int(e["group"])
+    for x, g, t, to, aux in np.asarray(events).tolist():  # (abi.EVENT_DTYPE's field order)
         s = state.get(g)
         if s is None:
             rr = runs.get(g) if isinstance(runs, dict) else runs[g]
@@ -66,7 +65,6 @@ def replay_votes(events, groups0, runs, peers, self_id):
                             last_term(groups0[g], rr)]
         if s[3]:  # faulted: the replay ended
             continue
-        t, to, aux, x = int(e["type"]), int(e["to"]), int(e["aux"]), int(e["x"])
         if t == abi.HB_EV_TERM:
             s[0] = x
         elif t == abi.HB_EV_LAST:

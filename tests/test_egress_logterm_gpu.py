@@ -460,7 +460,8 @@ def test_loopback_catch_up_below_the_boundary(monkeypatch):
     from .ingest_util import follow_reference
     from .parity_util import assert_events_equal, assert_groups_equal
     from .test_encode_ents_gpu import _source
-    from .test_frame_gpu import _build_dir, _dev, _host, _ids, _receive, _send_chain
+    from .cluster_util import receive as _receive, send_chain as _send_chain
+    from .test_frame_gpu import _build_dir, _dev, _host, _ids
     from .test_ingest_gpu import _with_sentinel
     monkeypatch.delenv("HB_SMALL_STEP", raising=False)
     n, K = 3, 20

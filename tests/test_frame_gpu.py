@@ -10,6 +10,8 @@ import pytest
 
 from etcd_amd import abi, frame, hipbatch
 
+from .cluster_util import receive as _receive, send_chain as _send_chain  # noqa: F401  (the device chain lives there)
+
 pytestmark = pytest.mark.gpu
 
 FILL = 0xAA
@@ -503,53 +505,6 @@ def test_unframe_host_checks(monkeypatch):
 
 
 # ---- 4. two hops through frames, the slots permuted --------------------------------------------
-def _send_chain(eng, self_id, seq, cap, npeers, gid_col, dsrc=None, bytes_per=91):
-    """hb_egress -> hb_egress_bin -> hb_encode[_ents] -> hb_peer_spans -> hb_frame on the engine's
-    stream: six calls, no host read between them.  Device tensors."""
-    import torch
-    t = lambda dt, fill, k=cap: torch.full((max(k, 1),), fill, dtype=dt, device="cuda")  # noqa: E731
-    tdt = {"<u4": torch.int32, "<u8": torch.int64}
-    raw = {name: t(tdt[dt], -1) for name, dt in abi.OUT_BATCH_FIELDS}
-    out = {name: t(tdt[dt], -1) for name, dt in abi.OUT_BATCH_FIELDS}
-    count, total = t(torch.int64, -1, 1), t(torch.int64, -1, 1)
-    bin_off, span, ispan = t(torch.int64, -1, npeers + 2), t(torch.int64, -1, npeers + 2), t(torch.int64, -1, npeers + 2)
-    fstat = t(torch.int32, -1, npeers + 1)
-    data, off, status = t(torch.uint8, FILL, cap * bytes_per), t(torch.int64, -1, cap + 1), t(torch.uint8, 0xEE)
-    index = t(torch.uint8, FILL, frame.isize(cap) + 64 * npeers)
-    eng.egress(self_id, raw, cap, count)
-    eng.egress_bin(raw, cap, out, bin_off, n_dev=count)
-    if dsrc is None:
-        eng.encode(self_id, out, cap, data, off, status, total, n_dev=count)
-    else:
-        eng.encode_ents(self_id, out, cap, dsrc, data, off, status, total, n_dev=count)
-    eng.peer_spans(off, bin_off, span)
-    eng.frame(self_id, seq, out, off, status, bin_off, span, gid_col, index, ispan, fstat)
-    return dict(out=out, count=count, total=total, bin_off=bin_off, span=span, ispan=ispan, fstat=fstat, data=data,
-                off=off, status=status, index=index)
-
-
-def _receive(pair, self_id, ch, peer_bin, sender, d, nrec, ent_cap):
-    """One peer's two spans into hb_unframe -> hb_decode_follow -> step_decoded.  The only host reads
-    are the four span words a transport needs to ship them."""
-    import torch
-    sp, isp = _host(ch["span"], np.uint64), _host(ch["ispan"], np.uint64)
-    fr = [(int(isp[peer_bin]), int(isp[peer_bin + 1] - isp[peer_bin]), int(sp[peer_bin]),
-           int(sp[peer_bin + 1] - sp[peer_bin]), sender)]
-    assert frame.rows(fr[0][1]) == nrec
-    full = lambda k, dt: torch.full((max(k, 1),), -0x11111112, dtype=dt, device="cuda")  # noqa: E731
-    off, ln, grp = full(nrec, torch.int64), full(nrec, torch.int32), full(nrec, torch.int32)
-    fst, unk = full(1, torch.int32), full(1, torch.int64)
-    fout = {k: full(nrec + 1, torch.int32 if k in ("group", "info") else torch.int64)
-            for k in ("group", "info", "term", "index", "hint", "commit", "eoff")}
-    fout["eterm"], fout["edesc"] = full(ent_cap, torch.int64), full(ent_cap, torch.int32)
-    edata, n_ent = full(ent_cap, torch.int64), full(1, torch.int64)
-    dstatus = torch.full((nrec,), 0xEE, dtype=torch.uint8, device="cuda")
-    pair.eng.unframe(self_id, ch["index"], fr, d, len(ch["data"]), off, ln, grp, fst, unk)
-    pair.eng.decode_follow(ch["data"], off, ln, grp, fout, dstatus, ent_cap, edata, n_ent)
-    pair.eng.step_decoded(fout, ent_cap)
-    return dict(off=off, ln=ln, grp=grp, fst=fst, unk=unk, dstatus=dstatus, n_ent=n_ent, frames=fr)
-
-
 def test_two_hops_through_frames_with_permuted_slots(monkeypatch):
     """tests/test_encode_ents_gpu.py::test_loopback_device_to_device's scenario, but the receiver gets
     nothing of the sender's arrays: node 2 holds group g at slot perm[g], the two nodes share only the

@@ -7,11 +7,14 @@ SnapshotMetadata :1201-1234, ConfState :1374-1392, Entry, encodeVarintRaft
 :1446-1454).  pb_message builds the same schema (raft/raftpb/raft.proto) with
 the protobuf library, an encoder independent of both decoders.
 """
+from functools import lru_cache
+
 import numpy as np
 
 from etcd_amd import abi
 
 
+@lru_cache(maxsize=1 << 16)
 def varint(v):
     v &= (1 << 64) - 1
     out = bytearray()
@@ -22,6 +25,7 @@ def varint(v):
     return bytes(out)
 
 
+@lru_cache(maxsize=None)
 def key(field, wt):
     return varint((field << 3) | wt)
 
@@ -44,6 +48,9 @@ def _snapshot(snap):
     return b + key(2, 2) + varint(len(meta)) + meta
 
 
+_NO_SNAPSHOT = _snapshot(None)
+
+
 def gogo_marshal(type, to=0, frm=0, term=0, log_term=0, index=0, entries=(), commit=0, snapshot=None,
                  reject=False, hint=0):
     """Message.MarshalTo: every required field, in field order, entries and
@@ -53,7 +60,7 @@ def gogo_marshal(type, to=0, frm=0, term=0, log_term=0, index=0, entries=(), com
     for e in entries:
         eb = _entry(e)
         b += key(7, 2) + varint(len(eb)) + eb
-    sb = _snapshot(snapshot)
+    sb = _snapshot(snapshot) if snapshot else _NO_SNAPSHOT
     b += key(8, 0) + varint(commit) + key(9, 2) + varint(len(sb)) + sb
     b += key(10, 0) + bytes([1 if reject else 0]) + key(11, 0) + varint(hint)
     return b
