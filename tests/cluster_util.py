@@ -23,6 +23,15 @@ hands a record to the host (a hole in the frame) the harness plays the host: a f
 MsgProp (HB_WIRE_SPLICE, by design) is completed with etcd_amd.splice from the entries of the
 proposal's arrival, an HB_OUT_HOST record from (A)'s message; the completed bytes travel beside
 the frame and take the hole's row at the receiver.
+
+The `compacting` scenarios add log compaction: every node's application compacts at committed -
+keep on every k-th round (Raft.compact / OracleGroups.compact / hb_set_log_bounds), the rings are
+reserved by compact_util's rule before every call, and a follower that fell below a leader's
+firstIndex is caught up with a MsgSnap.  HB_EV_SNAP makes no record, so the harness plays the host
+once more: it builds the message from the event, ships it beside the frame, gives it a row of its
+own at the receiver (after the rows its sender's frame holds for the group from before the event),
+and writes the HB_MSG_SNAP record into that row of the decoded batch, which hb_decode_follow left
+to the host.  The transport's ReportSnapshot comes back a round later as a local MsgSnapStatus row.
 """
 import numpy as np
 
@@ -33,9 +42,10 @@ from oracle.pyoracle import Msg, OracleGroups, Raft
 
 from . import props_util as PU
 from . import wire_util as W
+from .compact_util import _Compacting
 from .egress_app_util import is_app, marshal, status_of
 from .egress_bin_util import bin_reference
-from .egress_limit_util import follower_rewrites
+from .egress_limit_util import follower_rewrites, szlo_final
 from .egress_logterm_util import lookup_sends, replay_apps_logterm, ring_oldest
 from .egress_vote_util import oracle_older_runs
 from .encode_ents_util import build_source, encode_ents_reference, records_of
@@ -45,9 +55,10 @@ NO_LIMIT = abi.HB_NO_LIMIT
 RUN_CAP = 64      # term-run ring capacity reserved for every group: no run is ever dropped
 SIZE_CAP = 1024   # size ring capacity: no cumulative size is ever dropped
 M32 = 0xFFFFFFFF
-OK, HOST, SPLICE = abi.HB_WIRE_OK, abi.HB_WIRE_HOST, abi.HB_WIRE_SPLICE
+OK, HOST, SPLICE, LOCAL = abi.HB_WIRE_OK, abi.HB_WIRE_HOST, abi.HB_WIRE_SPLICE, abi.HB_WIRE_LOCAL
 RECORD_EVENTS = (abi.HB_EV_APP, abi.HB_EV_VOTE, abi.HB_EV_RESP, abi.HB_EV_HEARTBEAT)
 BATCH = ("group", "info", "term", "index", "hint", "commit")
+SNAP_DATA = b"app state"  # Snapshot.Data of every MsgSnap (its ConfState names the three nodes)
 
 
 def others(v):
@@ -63,8 +74,9 @@ class Scenario:
 
     def __init__(self, name, limit=NO_LIMIT, moving=False, G=96, capacity=128, rounds=52, W=8, seed=11,
                  partition=(1, 8, 22), drop=0.01, election=(8, 4, 6), favour=(0.4, 0.3, 0.3), lens=(None, 0, 1, 5, 16, 40),
-                 rate=0.5):
+                 rate=0.5, compact=None):
         self.name, self.limit, self.moving, self.G, self.capacity = name, limit, moving, G, capacity
+        self.compact = compact  # (k, keep): on every k-th round the application compacts at committed - keep
         self.rounds, self.W, self.seed, self.partition, self.election, self.lens = rounds, W, seed, partition, election, lens
         rng = np.random.default_rng(seed)
         ids = set()
@@ -101,13 +113,87 @@ class Scenario:
         return bool((lo <= r < hi and p in (s, d)) or self.lost[r, phase, s, d])
 
     @property
+    def compacting(self):
+        return self.compact is not None
+
+    @property
     def sized(self):
         return self.limit not in (0, NO_LIMIT)
 
 
 def msg_bytes(d):
+    snap = d.get("snap")
     return W.gogo_marshal(d["type"], to=d["to"], frm=d["frm"], term=d["term"], log_term=d["log_term"], index=d["index"],
-                          entries=d["ents"], commit=d["commit"], reject=d["reject"], hint=d["hint"])
+                          entries=d["ents"], commit=d["commit"], reject=d["reject"], hint=d["hint"],
+                          snapshot=None if snap is None else (SNAP_DATA, NODES) + snap)
+
+
+def is_snap(d):
+    return d["type"] == abi.HB_MSG_SNAP
+
+
+def slot_of(node):
+    return NODES.index(node)
+
+
+class Log:
+    """One group's entries in a node's store, from index `first` on: [(term, desc, Data, Entry.Size())]."""
+
+    def __init__(self):
+        self.first, self.ents = 1, []
+
+    @property
+    def next(self):
+        return self.first + len(self.ents)
+
+    def __getitem__(self, i):
+        assert self.first <= i < self.next, f"entry {i} of a store that holds [{self.first}, {self.next})"
+        return self.ents[i - self.first]
+
+    def cut(self, lo):
+        """Everything from index lo on leaves (a conflicting append)."""
+        del self.ents[max(lo, self.first) - self.first:]
+
+    def drop_below(self, first):
+        """The application compacted: the store starts at `first`."""
+        assert self.first <= first <= self.next
+        del self.ents[:first - self.first]
+        self.first = first
+
+    def restart(self, first):
+        """A restore: nothing but the snapshot below `first`."""
+        self.first, self.ents = first, []
+
+
+class Rings(_Compacting):
+    """compact_util's reserve rule and capacity prediction for one node's groups (`eng`: the node's
+    SlotView on the device, None in the twin)."""
+
+    def __init__(self, og, sized):
+        self.og, self.sized, self.eng, self.gpu = og, sized, None, False
+        self._start(None, None)
+        self.pushed = np.zeros(self.G, np.int64)  # entries appended since the group's last restore
+
+    def attach(self, eng):
+        self.eng, self.gpu = eng, True
+        self.check_capacity("load")
+
+    def before(self, batch=None, extra=0):
+        """Before a step or a tick: hb_reserve_log by the rule."""
+        self.reserve(batch, extra)
+        self.b4 = self._before()
+
+    def after(self, ev):
+        """After it: the counters, and every 8th call hb_log_capacity against the prediction."""
+        appended = self.appended.copy()
+        self._after(self.b4, ev)
+        self.pushed += self.appended - appended
+        f = ev[(ev["type"] == abi.HB_EV_FOLLOW) & (ev["aux"] == abi.HB_FOLLOW_RESTORE)]
+        self.pushed[f["group"].astype(np.int64)] = 0
+
+    def wrapped(self):
+        """The groups whose size ring has dropped an element since it last restarted."""
+        return self.pushed >= self.cap_sz
 
 
 # ---- (A) the reference cluster ----------------------------------------------------------------
@@ -123,6 +209,7 @@ class RefCluster:
                 r.r.elapsed, r.r.rand_pos = int(sc.elapsed0[v][g]), int(sc.rand_pos0[v][g])
                 self.rafts[v].append(r)
         self.led = {}  # (group, term) -> node
+        self.snap_groups, self.restored, self.restored_led = set(), set(), set()
 
     def _bump(self, k, n=1):
         self.count[k] = self.count.get(k, 0) + n
@@ -151,6 +238,10 @@ class RefCluster:
                     self._bump("app_ents")
                     if m.Index + m.nents < r.lastIndex:
                         self._bump("app_cut")
+                    if m.Index == r.firstIndex - 1 and r.firstIndex > 1:
+                        self._bump("app_at_boundary")  # LogTerm is the dummy entry's
+                    if (v, g) in self.restored:
+                        self.restored_led.add(g)       # a node that restored the group sends from its store
                 if m.LogTerm < m.Term:
                     self._bump("app_below_term")
             elif m.Type == abi.HB_MSG_PROP:
@@ -160,7 +251,11 @@ class RefCluster:
                 self._bump("app_resp_reject")
             elif m.Type == abi.HB_MSG_VOTE_RESP and m.Reject:
                 self._bump("vote_resp_reject")
-            assert m.Type != abi.HB_MSG_SNAP
+            elif m.Type == abi.HB_MSG_SNAP:
+                assert self.sc.compacting and m.snap_index == r.firstIndex - 1
+                d["snap"] = (m.snap_index, m.snap_term or r.term(m.snap_index))
+                self._bump("snap_sent")
+                self.snap_groups.add((g, m.To))
             d["bytes"] = msg_bytes(d)
             out.append(d)
         if r.state == abi.HB_STATE_LEADER and payloads is not None:
@@ -176,15 +271,31 @@ class RefCluster:
             return Msg(d["type"], From=d["frm"], To=d["to"], Entries=len(d["ents"]), edesc=[desc_of(e[3]) for e in d["ents"]])
         return Msg(d["type"], From=d["frm"], To=d["to"], Term=d["term"], Index=d["index"], LogTerm=d["log_term"],
                    Commit=d["commit"], Reject=d["reject"], RejectHint=d["hint"], Entries=[(e[2], e[1]) for e in d["ents"]],
-                   edesc=[desc_of(e[3]) for e in d["ents"]])
+                   edesc=[desc_of(e[3]) for e in d["ents"]], Snapshot=d.get("snap"))
 
-    def phase1(self, v, inbox, props):
+    def phase1(self, v, inbox, props, reports=()):
+        """The frames' messages, the transport's ReportSnapshot calls [(group, to, reject)] as local
+        MsgSnapStatus, the clients' proposals."""
         out = []
         for d in inbox:
             r = self.rafts[v][d["g"]]
-            last0 = r.lastIndex
+            last0, first0 = r.lastIndex, r.firstIndex
             r.Step(self._orc(d))
+            if is_snap(d):
+                if r.firstIndex != first0:
+                    assert (r.firstIndex, r.lastIndex, r.committed) == (d["snap"][0] + 1,) + (d["snap"][0],) * 2
+                    self._bump("snap_restored")
+                    self.restored.add((v, d["g"]))
+                else:
+                    self._bump("snap_ignored")
+                last0 = r.lastIndex
             out += self._drain(v, d["g"], last0, [e[3] for e in d["ents"]] if d["type"] == abi.HB_MSG_PROP else None)
+        for g, to, reject in reports:
+            r = self.rafts[v][g]
+            last0 = r.lastIndex
+            r.Step(Msg(abi.HB_MSG_SNAP_STATUS, From=to, To=v, Reject=reject))
+            out += self._drain(v, g, last0, None)
+            self._bump("snap_status_reject" if reject else "snap_status_ok")
         for g, pl in props:
             r = self.rafts[v][g]
             last0 = r.lastIndex
@@ -199,6 +310,19 @@ class RefCluster:
             r.tick()
             out += self._drain(v, g, last0, None)
         return out
+
+    def compact(self, v):
+        """Node v's application compacts every group whose committed - keep lies above its firstIndex,
+        there, with a snapshot: (groups, indices)."""
+        gs, at = [], []
+        for g, r in enumerate(self.rafts[v]):
+            i = r.committed - self.sc.compact[1]
+            if i > r.firstIndex:
+                assert r.compact(i, snapshot=True) == 0
+                gs.append(g)
+                at.append(i)
+        self._bump("compactions", len(gs))
+        return gs, at
 
     def groups(self, v):
         return np.array([np.frombuffer(bytes(r.to_group()), dtype=abi.GROUP_DTYPE)[0] for r in self.rafts[v]],
@@ -239,7 +363,8 @@ class NodeRef:
         self.peers[:, :3] = NODES
         self.slot = sc.perm[v].copy()
         self.store = {}   # (group, index, term) -> (desc, Data or None): what this node's host saw on the wire
-        self.log = [[] for _ in range(G)]  # per group [(term, desc, Data, Entry.Size())] of entries 1 ..
+        self.log = [Log() for _ in range(G)]  # per group the entries from the first held index on
+        self.rings = Rings(self.og, sc.sized) if sc.compacting else None
         self.count = {}
         self.arrivals = {}
         self.commit_seen = np.zeros(G, np.int64)
@@ -269,12 +394,20 @@ class NodeRef:
         return p, n
 
     # -- receive ---------------------------------------------------------------------------------
-    def assemble(self, emissions, props):
-        """The transport: emissions = [(sender, frame bytes, span bytes, [(row, bytes)])] in delivery
-        order, props = [(group, [Data])] of this node's clients.  One index buffer, one byte buffer,
-        the frame list of hb_unframe, the host's rows (frame row -> bytes) and the extra records."""
-        index, data, frames, fills, base = b"", b"", [], [], 0
-        for s, fr, sp, fl in emissions:
+    def assemble(self, emissions, props, reports=()):
+        """The transport: emissions = [(sender, frame bytes or None, span bytes, [(row, bytes)], [MsgSnap])]
+        in delivery order, props = [(group, [Data])] of this node's clients, reports = [(group, to,
+        reject)] of its own ReportSnapshot calls.  One index buffer, one byte buffer, the frame list
+        of hb_unframe, the host's rows (frame row -> bytes), the MsgSnap rows (each where its sender's
+        events put it among the frame's rows of its group) and the extra records."""
+        index, data, frames, fills, snaps, base = b"", b"", [], [], [], 0
+        for s, fr, sp, fl, sn in emissions:
+            gids = frame.parse_index(fr)["gid"] if fr is not None else np.zeros(0, np.uint64)
+            for d in sn:  # after the `before` rows the frame has for its group, before the next one
+                mine = np.nonzero(gids == self.sc.gid[d["g"]])[0]
+                snaps.append((base + (int(mine[d["before"]]) if d["before"] < len(mine) else len(gids)), d))
+            if fr is None:
+                continue
             assert len(index) % 8 == 0
             frames.append((len(index), len(fr), len(data), len(sp), s))
             index += fr
@@ -282,12 +415,17 @@ class NodeRef:
             fills += [(base + j, fr, j, b) for j, b in fl]
             base += frame.rows(len(fr))
         extra = []
+        for g, to, reject in reports:
+            extra.append((g, W.gogo_marshal(abi.HB_MSG_SNAP_STATUS, to=self.v, frm=to, reject=reject),
+                          dict(info=abi.hb_info(abi.HB_MSG_SNAP_STATUS, slot_of(to), reject), term=0, index=0, hint=0)))
         for g, pl in props:
-            extra.append((g, PU.prop(pl, to=self.v, frm=self.v)))
-        return dict(index=index, data=data, frames=frames, fills=fills, extra=extra, nf=base)
+            extra.append((g, PU.prop(pl, to=self.v, frm=self.v), None))
+        return dict(index=index, data=data, frames=frames, fills=fills, snaps=snaps, extra=extra, nf=base)
 
     def rows(self, asm, uf, d):
-        """hb_unframe's rows, the holes the host fills patched in, the clients' proposals behind."""
+        """hb_unframe's rows, the holes the host fills patched in, the MsgSnap rows inserted where
+        assemble placed them, the ReportSnapshot rows and the clients' proposals behind.  Leaves
+        self.host_rows = [(row, the status the decoder must give it, the record the host writes)]."""
         off, ln, grp = (a.copy() for a in uf[:3])
         blob = bytearray(asm["data"])
         for row, fr, j, b in asm["fills"]:
@@ -295,8 +433,30 @@ class NodeRef:
             assert grp[row] == frame.NO_SLOT and ln[row] == 0
             off[row], ln[row], grp[row] = len(blob), len(b), d.lookup(gid) if gid else frame.NO_SLOT
             blob += b
+        self.host_rows = []
+        if asm["snaps"]:
+            at, so, sl, sg = [], [], [], []
+            final = np.zeros(len(asm["snaps"]), np.int64)  # (np.insert: ascending position, stable)
+            order = np.argsort([row for row, _ in asm["snaps"]], kind="stable")
+            final[order] = np.array([asm["snaps"][j][0] for j in order], np.int64) + np.arange(len(order))
+            for k, (row, m) in enumerate(asm["snaps"]):
+                slot = d.lookup(int(self.sc.gid[m["g"]]))  # (the host's directory)
+                assert slot == self.slot[m["g"]]
+                at.append(row)
+                so.append(len(blob))
+                sl.append(len(m["bytes"]))
+                sg.append(slot)
+                blob += m["bytes"]
+                self.host_rows.append((int(final[k]), HOST, dict(
+                    group=slot, info=abi.hb_info(abi.HB_MSG_SNAP, slot_of(m["frm"]), False), term=m["term"],
+                    index=m["snap"][0], hint=m["snap"][1])))
+            off = np.insert(off, at, np.array(so, np.uint64))
+            ln = np.insert(ln, at, np.array(sl, np.uint32))
+            grp = np.insert(grp, at, np.array(sg, np.uint32))
         xo, xl, xg = [], [], []
-        for g, b in asm["extra"]:
+        for g, b, rec in asm["extra"]:
+            if rec is not None:
+                self.host_rows.append((len(off) + len(xo), LOCAL, dict(rec, group=int(self.slot[g]))))
             xo.append(len(blob))
             xl.append(len(b))
             xg.append(int(self.slot[g]))
@@ -308,6 +468,19 @@ class NodeRef:
     def decode_ref(self, data, off, ln, grp):
         p, n = self.peers_cap()
         return PU.props_reference(data, off, ln, grp, self.C, n, p)
+
+    def host_write(self, dec, ctx):
+        """The host's records (MsgSnap, MsgSnapStatus) in their rows of a decoded batch.  The decoder
+        must have left each to the host: its status is asserted, and group 0xFFFFFFFF."""
+        if not self.host_rows:
+            return dec
+        out = dict(dec, **{k: dec[k].copy() for k in BATCH})
+        for row, st, rec in self.host_rows:
+            assert dec["status"][row] == st and dec["group"][row] == M32, \
+                f"{ctx}: row {row} for the host decodes with status {dec['status'][row]} group {dec['group'][row]}"
+            for k, x in rec.items():
+                out[k][row] = x
+        return out
 
     def batch_of(self, dec):
         """The decoded batch in oracle group numbers, sentinel included."""
@@ -383,19 +556,33 @@ class NodeRef:
         now = self.og.groups()
         assert not now["fault"].any(), f"node {self.v}: oracle fault"
         esz = pyoracle.lib().orc_entry_size
+        for g in ev["group"][(ev["type"] == abi.HB_EV_FOLLOW) & (ev["aux"] == abi.HB_FOLLOW_RESTORE)].tolist():
+            self.log[g].restart(int(now[g]["first_index"]))  # nothing but the snapshot, then what followed it
+            touched[g] = self.log[g].first
+            self._bump("restores")
         for g, lo in touched.items():
             log = self.log[g]
-            del log[lo - 1:]
-            for i in range(len(log) + 1, int(now[g]["last_index"]) + 1):
+            log.cut(lo)
+            for i in range(log.next, int(now[g]["last_index"]) + 1):
                 t = self.og.term(g, i)
                 d, p = self.store[(g, i, t)]
-                log.append((t, d, p, int(esz(d, t, i))))
+                log.ents.append((t, d, p, int(esz(d, t, i))))
         self.now, self.touched = now, touched
         assert (now["committed"].astype(np.int64) >= self.commit_seen).all(), f"node {self.v}: committed went back"
         self.commit_seen = now["committed"].astype(np.int64)
 
     def size_of(self, g, i):
-        return self.log[g][i - 1][3]
+        return self.log[g][i][3]
+
+    def compact(self, groups, index):
+        """The application compacted `groups` at `index` (with a snapshot): the batch oracle follows,
+        and the store drops what lies below the new firstIndex."""
+        rc = self.og.compact(np.array(groups, np.uint32), np.array(index, np.uint64), True)
+        assert not rc.any(), f"node {self.v}: compaction refused: {rc}"
+        self.now = self.og.groups()
+        for g, i in zip(groups, index):
+            assert (int(self.now[g]["first_index"]), int(self.now[g]["snap_index"])) == (i + 1, i)
+            self.log[g].drop_below(i + 1)
 
     def want(self, snap, ev):
         """The records hb_egress makes of the call (mode 7, both knobs, forwards), by group; the
@@ -405,8 +592,12 @@ class NodeRef:
         # (the replays read five fields of every group's record before the call: as plain dicts)
         names = ("term", "last_index", "term_first", "first_index", "committed")
         g0 = [dict(zip(names, row)) for row in zip(*(snap.groups[k].tolist() for k in names))]
-        oldest = ring_oldest(ev, g0, snap.runs, RUN_CAP)
-        szlo = {g: int(info[g, 1]) for g in range(self.G)}
+        if self.rings is None:
+            oldest = ring_oldest(ev, g0, snap.runs, RUN_CAP)
+            szlo = {g: int(info[g, 1]) for g in range(self.G)}
+        else:  # the rings at the capacities the reserve rule gave them
+            oldest = ring_oldest(ev, g0, snap.runs, self.rings.cap_tr)
+            szlo = {g: szlo_final(info[g, 1], info[g, 3], self.rings.cap_sz[g]) for g in range(self.G)}
         lim = (self.size_of, szlo) if sc.sized else None
         whole_ev = replay_apps_logterm(ev, g0, snap.runs, self.peers, v, self.og.term, oldest,
                                        max_msg_size=sc.limit, limit=lim, votes=True)
@@ -453,12 +644,26 @@ class NodeRef:
             return mine[:int(np.isin(e["type"], RECORD_EVENTS).sum())]  # (mode 7: one record per such event)
         return PU.merge_forwards(ev, recs, self.peers, v)
 
+    def snaps_of(self, snap, ev):
+        """The HB_EV_SNAP events of a call as [group, to, x, the Term at the send, the records the
+        group's earlier events of the call made for that peer], in event order."""
+        term, made, out = {}, {}, []
+        kinds = RECORD_EVENTS + (abi.HB_EV_PROP_FWD, abi.HB_EV_TERM, abi.HB_EV_SNAP)
+        for x, g, t, to, _ in ev[np.isin(ev["type"], kinds)].tolist():
+            if t == abi.HB_EV_TERM:
+                term[g] = x
+            elif t == abi.HB_EV_SNAP:
+                out.append([g, int(self.peers[g][to]), x, term.get(g, int(snap.groups[g]["term"])), made.get((g, to), 0)])
+            else:
+                made[(g, to)] = made.get((g, to), 0) + 1
+        return out
+
     def source(self, snap):
-        """hb_ent_source from the store: the whole log of every group this node led before the
-        call or leads after it, by slot."""
+        """hb_ent_source from the store: every entry it holds (from firstIndex on) of every group this
+        node led before the call or leads after it, by slot."""
         lead = (snap.groups["state"] == abi.HB_STATE_LEADER) | (self.now["state"] == abi.HB_STATE_LEADER)
-        win = {int(self.slot[g]): (1, [((d >> 30) & 1, t, p) for t, d, p, _ in self.log[g]])
-               for g in np.nonzero(lead)[0].tolist() if self.log[g]}
+        win = {int(self.slot[g]): (self.log[g].first, [((d >> 30) & 1, t, p) for t, d, p, _ in self.log[g].ents])
+               for g in np.nonzero(lead)[0].tolist() if self.log[g].ents}
         return build_source(win, self.C)
 
     # -- send ------------------------------------------------------------------------------------
@@ -543,7 +748,9 @@ class NodeRef:
 class Cluster:
     """(A) and (B) in lockstep; `device` = a factory (scenario, node, NodeRef) -> GpuNode puts (C)
     in the loop, None runs (B) in its place.  `tamper(what, round, node, phase, obj)` may corrupt the
-    device-role output of a decode or of a send chain (the sensitivity experiment)."""
+    device-role output of a decode ("decode"), of a send chain ("send"; in the twin also its "records"),
+    the HB_EV_SNAP events the host reads ("snaps") or the entry source it builds ("source"): the
+    sensitivity experiment."""
 
     def __init__(self, sc, device=None, tamper=None):
         self.sc, self.tamper = sc, tamper
@@ -552,9 +759,11 @@ class Cluster:
         self.dev = {v: device(sc, v, self.B[v]) for v in NODES} if device is not None else None
         for v in NODES:
             assert np.array_equal(self.B[v].og.groups(), self.A.groups(v)), "the oracle's record of a new group"
-        self.flight = {v: [] for v in NODES}    # (sender, frame, span, fills) on their way to v
+        self.flight = {v: [] for v in NODES}    # (sender, phase, frame, span, fills, MsgSnap) on their way to v
         self.a_flight = {v: [] for v in NODES}  # (A)'s messages on their way to v
+        self.reports = {v: [] for v in NODES}   # (group, to, lost) of the MsgSnap v handed to its transport
         self.lead_hist, self.commit_hist = [], []
+        self.moved_wrapped = 0
         self.round = 0
 
     def _send(self, v, phase, snap, ev, a_out, ctx):
@@ -562,28 +771,75 @@ class Cluster:
         want = b.want(snap, ev)
         src = b.source(snap)
         seq = 2 * self.round + phase
+        if self.tamper is not None:
+            self.tamper("source", self.round, v, phase, src)
         if self.dev is None:
+            if self.tamper is not None:
+                self.tamper("records", self.round, v, phase, want)
             raw = b.to_slots(want)
             em = b.emit_ref(raw, src, seq)
         else:
             em = self.dev[v].send(b, want, src, seq, ctx)
         if self.tamper is not None:
             self.tamper("send", self.round, v, phase, em)
-        res = b.reconcile(em, a_out, ctx)
+        self._check_snaps(v, phase, snap, ev, a_out, ctx)
+        res = b.reconcile(em, [d for d in a_out if not is_snap(d)], ctx)
         for u in others(v):
-            if sc.dropped(self.round, phase, v, u):
+            snaps = [d for d in a_out if d["to"] == u and is_snap(d)]
+            lost = sc.dropped(self.round, phase, v, u)
+            self.reports[v] += [(d["g"], u, lost) for d in snaps]  # the transport's ReportSnapshot, a round later
+            if lost:
+                if snaps:
+                    self.A._bump("snap_lost", len(snaps))
                 continue
             fr, sp, fills = res[u]
-            if len(fr):
-                self.next_flight[u].append((v, phase, fr, sp, fills))
+            if len(fr) or snaps:
+                self.next_flight[u].append((v, phase, fr if len(fr) else None, sp, fills, snaps))
             self.next_a[u] += [(v, phase, d) for d in a_out if d["to"] == u]
+
+    def _check_snaps(self, v, phase, snap, ev, a_out, ctx):
+        """HB_EV_SNAP makes no record: the events (group, to, x) are (A)'s MsgSnap of the call, in
+        order per group, and the message the host builds of each (Term of the send, the snapshot's
+        term from the log) is (A)'s, byte for byte.  The events also place the MsgSnap in its peer's
+        stream: after as many records of the group as (A) sent that peer messages before it."""
+        b = self.B[v]
+        got = b.snaps_of(snap, ev)
+        if self.tamper is not None:
+            self.tamper("snaps", self.round, v, phase, got)
+        assert self.sc.compacting or not got
+        mine, seen = {}, {}
+        for i, d in enumerate(a_out):
+            if is_snap(d):
+                mine.setdefault(d["g"], []).append(d)
+                d["before"] = sum(e["g"] == d["g"] and e["to"] == d["to"] and not is_snap(e) for e in a_out[:i])
+                if d["before"]:
+                    self.A._bump("snap_after_records")
+        for g, to, x, term, before in got:
+            k = seen.get(g, 0)
+            seen[g] = k + 1
+            assert k < len(mine.get(g, ())), f"{ctx}: group {g}: HB_EV_SNAP to {to} at {x} beyond the reference's MsgSnap"
+            a = mine[g][k]
+            assert (to, x, before) == (a["to"], a["snap"][0], a["before"]), \
+                f"{ctx}: group {g}: HB_EV_SNAP ({to}, {x}) after {before} records for {a}"
+            full = W.gogo_marshal(abi.HB_MSG_SNAP, to=to, frm=v, term=term, snapshot=(SNAP_DATA, NODES, x, b.og.term(g, x)))
+            assert full == a["bytes"], f"{ctx}: group {g}: the host's MsgSnap {full.hex()} for {a['bytes'].hex()}"
+        assert {g: len(m) for g, m in mine.items()} == seen, f"{ctx}: a MsgSnap of the reference without its HB_EV_SNAP"
+
+    def _compact(self, v, ctx):
+        """The application of node v compacts on all three layers."""
+        gs, at = self.A.compact(v)
+        b = self.B[v]
+        b.compact(gs, at)
+        if self.dev is not None:
+            self.dev[v].compact(b, gs, ctx)
+        self._check_state(v, ctx)
 
     def _check_store(self, v, ctx):
         """Every entry the call put into the node's log store is the registry's: descriptor and bytes."""
         b = self.B[v]
         for g, lo in b.touched.items():
-            for i in range(lo, len(b.log[g]) + 1):
-                t, d, p, _ = b.log[g][i - 1]
+            for i in range(max(lo, b.log[g].first), b.log[g].next):
+                t, d, p, _ = b.log[g][i]
                 q = self.A.registry.get((g, i, t), b)
                 assert q is not b and (d, p) == (desc_of(q), q), f"{ctx}: group {g} entry {i} term {t}: stored {(d, p)}, proposed {q}"
 
@@ -601,11 +857,12 @@ class Cluster:
         for v in NODES:
             b, ctx = self.B[v], f"{sc.name} round {r} node {v} step"
             key = lambda e: (e[0], e[1])  # noqa: E731  (ascending sender, phase 1 before phase 2)
-            ems = [(s, fr, sp, fl) for s, _, fr, sp, fl in sorted(self.flight[v], key=key)]
+            ems = [(s, fr, sp, fl, sn) for s, _, fr, sp, fl, sn in sorted(self.flight[v], key=key)]
             inbox = [d for _, _, d in sorted(self.a_flight[v], key=key)]
             props = sc.props[r][v]
-            a_out = self.A.phase1(v, inbox, props)
-            asm = b.assemble(ems, props)
+            reports, self.reports[v] = self.reports[v], []
+            a_out = self.A.phase1(v, inbox, props, reports)
+            asm = b.assemble(ems, props, reports)
             d = b.directory()
             uf = frame.unframe(asm["index"], asm["frames"], v, d.lookup)
             assert not uf[3].any() and uf[4] == 0, f"{ctx}: fstatus {uf[3]} unknown {uf[4]}"
@@ -613,31 +870,48 @@ class Cluster:
                 self.dev[v].unframe(b, asm, uf, ctx)
             off, ln, grp, data = b.rows(asm, uf, d)
             dec = b.decode_ref(data, off, ln, grp)
-            bad = np.nonzero((dec["status"] != OK) & (grp != frame.NO_SLOT))[0]
+            mine = np.ones(len(off), bool)
+            mine[[row for row, _, _ in b.host_rows]] = False  # (host_write asserts what those decode to)
+            bad = np.nonzero((dec["status"] != OK) & (grp != frame.NO_SLOT) & mine)[0]
             assert len(bad) == 0, f"{ctx}: rows {bad[:5]} decode with status {dec['status'][bad[:5]]}"
-            batch = b.batch_of(dec)
+            patched = b.host_write(dec, ctx)
+            batch = b.batch_of(patched)
+            if b.rings is not None:
+                b.rings.before(batch)
             if self.dev is not None:
-                dec = self.dev[v].decode_step(b, data, off, ln, grp, dec, ctx)
+                patched = self.dev[v].decode_step(b, data, off, ln, grp, dec, ctx)
             if self.tamper is not None:
-                self.tamper("decode", r, v, 0, dec)
-            snap, ev, st = b.step(batch, dec, data)
+                self.tamper("decode", r, v, 0, patched)
+            snap, ev, st = b.step(batch, patched, data)
             self._check_store(v, ctx)
             if self.dev is not None:
                 self.dev[v].check(b, ev, st, ctx)
+            if b.rings is not None:
+                b.rings.after(ev)
             self._check_state(v, ctx)
             self._send(v, 0, snap, ev, a_out, ctx)
         for v in NODES:
             b, ctx = self.B[v], f"{sc.name} round {r} node {v} tick"
             a_out = self.A.phase2(v)
+            if b.rings is not None:
+                b.rings.before(extra=1)
             snap, ev, st = b.tick()
             if self.dev is not None:
                 self.dev[v].tick()
                 self.dev[v].check(b, ev, st, ctx, stepped=False)
+            if b.rings is not None:
+                b.rings.after(ev)
             self._check_state(v, ctx)
             self._send(v, 1, snap, ev, a_out, ctx)
+        if sc.compacting and r % sc.compact[0] == sc.compact[0] - 1:
+            for v in NODES:
+                self._compact(v, f"{sc.name} round {r} node {v} compact")
         if sc.moving:
             for v in NODES:
                 src, dst = self.B[v].random_move()
+                if self.B[v].rings is not None:
+                    inv = self.B[v].inverse()
+                    self.moved_wrapped += int(self.B[v].rings.wrapped()[inv[dst[src != dst]]].sum())
                 if self.dev is not None:
                     self.dev[v].move(src, dst, self.B[v])
         self.flight, self.a_flight = self.next_flight, self.next_a
@@ -657,9 +931,10 @@ class Cluster:
             b = self.B[v]
             assert not b.now["fault"].any()
             for g in range(sc.G):
-                c = int(b.now[g]["committed"])
-                for i in range(1, c + 1):
-                    t, d, p, _ = b.log[g][i - 1]
+                c, first = int(b.now[g]["committed"]), int(b.now[g]["first_index"])
+                assert int(b.now[g]["snap_index"]) <= c and b.log[g].first == first
+                for i in range(first, c + 1):
+                    t, d, p, _ = b.log[g][i]
                     assert (g, i, t) in self.A.registry, f"node {v} group {g}: entry {i} of term {t} is nobody's"
                     q = self.A.registry[(g, i, t)]
                     assert (d, p) == (desc_of(q), q), f"node {v} group {g} entry {i}: {(d, p)} for {q}"
@@ -675,15 +950,63 @@ class Cluster:
 
 # ---- the scenarios and what they must reach ---------------------------------------------------------
 LIMIT = 150
+COMPACTING = dict(compact=(2, 4), partition=(1, 7, 22))  # every 2nd round at committed - 4; node 1 cut off a round earlier
 
 
 def scenario(name, **over):
     """elections: no limit; limited: MaxSizePerMsg 150 with payloads of 0 to 64 bytes, so that limitSize
     cuts and the windows of 8 fill; moving: every node moves a third of its groups after every round.
     All three: 52 rounds, node 1 is cut off for rounds 8 to 21, every frame is lost with probability 0.01, every
-    node proposes 1 to 3 entries to half of its groups in every round (followers forward them)."""
-    kw = dict(elections={}, limited=dict(limit=LIMIT, lens=(None, 0, 1, 7, 16, 33, 64)), moving=dict(moving=True))[name]
+    node proposes 1 to 3 entries to half of its groups in every round (followers forward them).
+    compacting: limited, and every node compacts every group at committed - 4 after every second round, the
+    rings reserved by need before every call; node 1 is cut off from round 7, so that enough probes still go
+    below the leaders' boundaries.  compacting_moving: compacting with moving's moves."""
+    limited = dict(limit=LIMIT, lens=(None, 0, 1, 7, 16, 33, 64))
+    kw = dict(elections={}, limited=limited, moving=dict(moving=True),
+              compacting=dict(limited, **COMPACTING), compacting_moving=dict(limited, moving=True, **COMPACTING))[name]
     return Scenario(name, **dict(kw, **over))
+
+
+def compacting_conditions(c, L, cm, n):
+    """What the compacting scenarios must reach beyond the others: the figures first,
+    then the conditions on them."""
+    sc = c.sc
+    p, lo, hi = sc.partition
+    followed = np.nonzero((L[lo - 1] != p) & (L[lo - 1] != 0))[0]
+    caught = [g for g in followed.tolist() if (g, p) in c.A.snap_groups]
+    # a group that got a snapshot has caught up: by the last round every node has passed the highest
+    # `committed` any node held at the heal (on top of least_advance, which check_conditions asserts)
+    got = sorted({g for g, _ in c.A.snap_groups})
+    past = cm[-1][:, got].min(axis=0) - cm[hi - 1][:, got].max(axis=0)
+    caps, once, twice, runs = {}, [], [], []
+    for v in NODES:
+        rg = c.B[v].rings
+        last = c.B[v].og.log_info().astype(np.int64)[:, 3]
+        once.append(int((last - 1 >= rg.cap_sz).sum()))
+        twice.append(int((last - 1 >= 2 * rg.cap_sz).sum()))
+        runs.append(int(rg.runs_started.max()))
+        for k in zip(rg.cap_sz.tolist(), rg.cap_tr.tolist()):
+            caps[k] = caps.get(k, 0) + 1
+    f = dict(snap_groups_of_cut_node=len(caught), followed_by_cut_node=len(followed), snap_groups=len(got),
+             least_past_the_heal=int(past.min()) if len(got) else 0,
+             final_spread=int((cm[-1][:, got].max(axis=0) - cm[-1][:, got].min(axis=0)).max()) if len(got) else 0,
+             restored_led=len(c.A.restored_led), capacities=dict(sorted(caps.items())), size_ring_wrapped=once,
+             size_ring_wrapped_twice=twice, most_runs_started=runs, moved_wrapped=c.moved_wrapped)
+    assert len(caught) >= len(followed) / 2 and len(followed) >= sc.G // 4, f
+    assert f["least_past_the_heal"] >= 10, f
+    assert n.get("snap_restored", 0) >= 1 and n.get("snap_ignored", 0) >= 1, n
+    assert n.get("snap_lost", 0) >= 1 and n.get("snap_status_reject", 0) >= 1, n
+    assert n.get("app_at_boundary", 0) >= 1, n
+    assert f["restored_led"] >= 1, f
+    # The rings wrap, on every node: the size ring of at least half of the groups has passed its
+    # capacity, that of a few groups two capacities.  The capacity is each group's own under the
+    # reserve rule: the rule adds a call's messages and entries to the span, which keeps every group
+    # here above HB_SIZE_RING_MIN / HB_TERM_RING_MIN, and 52 rounds start at most 2 term runs in a
+    # group, so no run ring wraps (DESIGN.md §4.1 has the figures).
+    assert min(once) >= sc.G / 2 and min(twice) >= 4, f
+    if sc.moving:
+        assert c.moved_wrapped >= 1, f
+    return f
 
 
 def check_conditions(c):
@@ -712,6 +1035,8 @@ def check_conditions(c):
     assert n["B_splice_prop"] == n["prop_fwd"] and n["B_app"] == n["app"]
     handed = n.get("B_app_host", 0) + n.get("B_vote_host", 0)
     assert handed <= 0.01 * (n["B_app"] + n["B_vote"]), n
+    if sc.compacting:
+        n.update(compacting_conditions(c, L, cm, n))
     return dict(n, orphans=int(orphan.sum()), reelected=int((again & orphan).sum()), least_advance=int(adv.min()),
                 best_share=[round(x, 2) for x in share], handed_to_host=handed)
 
@@ -810,7 +1135,8 @@ class GpuNode:
         self.real.load_peers(peers)
         self.view.load_timers(b.timers0)
         self.real.set_rand(b.draws)
-        self.view.reserve_log(np.arange(sc.G), SIZE_CAP if sc.sized else None, RUN_CAP)
+        if not sc.compacting:
+            self.view.reserve_log(np.arange(sc.G), SIZE_CAP if sc.sized else None, RUN_CAP)
         self.real.set_egress(True, votes=True, apps=True)
         self.real.set_egress_logterm(True)
         self.real.set_wire_props(decode=True, egress=True)
@@ -820,8 +1146,11 @@ class GpuNode:
         assert self.real.egress_mode() == 7 and self.real.wire_props() == 3 and self.real.egress_logterm()
         assert self.real.egress_limit() == sc.sized
         assert_groups_equal(self.view.get_groups(), init, f"node {v} load")
-        self.caps = [self.view.log_capacity(g) for g in range(sc.G)]
-        assert all(c[1] >= RUN_CAP for c in self.caps)
+        if sc.compacting:  # the rings are reserved by need before every call: (B) predicts, the engine follows
+            b.rings.attach(self.view)
+        else:
+            self.caps = [self.view.log_capacity(g) for g in range(sc.G)]
+            assert all(c[1] >= RUN_CAP for c in self.caps)
         self._dir_for = None
 
     def close(self):
@@ -874,10 +1203,18 @@ class GpuNode:
         edata, n_ent = fill(ent_cap, torch.int64), fill(1, torch.int64)
         status = torch.full((n,), 0xEE, dtype=torch.uint8, device="cuda")
         self.real.decode_follow(dev(data), dev(off), dev(ln), dev(grp), out, status, ent_cap, edata, n_ent)
+        dt = dict(group=np.uint32, info=np.uint32, edesc=np.uint32)
+        if b.host_rows:  # the host reads what the decoder left to it and writes its records into those rows
+            self.real.sync()
+            got = {k: host(out[k], dt.get(k, np.uint64)) for k in out}
+            for row, _, rec in b.host_rows:
+                for k, x in rec.items():
+                    out[k][row:row + 1].copy_(dev(np.array([x], got[k].dtype)))
+            torch.cuda.synchronize()  # (the writes are torch's, the step the engine's stream)
         self.real.step_decoded(out, ent_cap)
         self.real.sync()
-        dt = dict(group=np.uint32, info=np.uint32, edesc=np.uint32)
-        got = {k: host(out[k], dt.get(k, np.uint64)) for k in out}
+        if not b.host_rows:
+            got = {k: host(out[k], dt.get(k, np.uint64)) for k in out}
         got.update(status=status.cpu().numpy(), edata=host(edata, np.uint64), n_ent=int(host(n_ent, np.uint64)[0]))
         assert got["n_ent"] == ne, f"{ctx}: n_ent {got['n_ent']} expected {ne}"
         _same(got["status"], ref["status"], "hb_decode_follow status", ctx)
@@ -887,7 +1224,7 @@ class GpuNode:
             _same(got[k][:ne], ref[k], f"hb_decode_follow {k}", ctx)
             assert (got[k][ne:].view(np.uint8) == 0xEE).all(), f"{ctx}: {k} written past the entry count"
             got[k] = got[k][:ne]
-        return got
+        return b.host_write(got, ctx)  # (what the device decoded, compared above; then what it stepped)
 
     def check(self, b, ev, st, ctx, stepped=True):
         """After the step or the tick: events, stats, every group record and timers, and after the step
@@ -970,6 +1307,17 @@ class GpuNode:
         self.view.move_slots(src, dst)
         assert np.array_equal(self.view.slot, b.slot)
 
-    def check_end(self):
+    def compact(self, b, groups, ctx):
+        """hb_set_log_bounds of the groups (B) just compacted, from its records."""
+        from .parity_util import assert_groups_equal
+        if len(groups):
+            gs = np.array(groups, np.uint32)
+            self.view.set_log_bounds(gs, b.now["first_index"][gs], b.now["snap_index"][gs])
+        assert_groups_equal(self.view.get_groups(), b.now, ctx)
+
+    def check_end(self, b):
+        if self.sc.compacting:
+            b.rings.check_capacity(f"node {self.v} end")
+            return
         for g in range(self.sc.G):
             assert self.view.log_capacity(g) == self.caps[g], f"group {g}: a ring was regrown"

@@ -11,6 +11,12 @@ order, hb_encode_ents' bytes, off and status, hb_peer_spans and hb_frame's index
 reference; and, independently, the per-peer byte stream with the messages the reference cluster of
 Raft objects sent to that peer.  The engines step what the other engines wrote, and a new leader
 re-sends entries from a store filled from hb_decode_follow's outputs alone.
+
+test_compacting / test_compacting_moving: the same under log compaction.  hb_set_log_bounds after
+every second round, hb_reserve_log by need before every call with hb_log_capacity compared with the
+prediction, HB_EV_SNAP against the reference's MsgSnap, the MsgSnap and MsgSnapStatus rows decoded
+as HB_WIRE_HOST / HB_WIRE_LOCAL and then written by the host into the decoded device batch, the
+restore in k_follow, and replication resumed from a source window that starts at firstIndex.
 """
 import pytest
 
@@ -28,7 +34,7 @@ def _run(name, monkeypatch, small=True):
     try:
         c.run().check_end()
         for v in NODES:
-            c.dev[v].check_end()
+            c.dev[v].check_end(c.B[v])
     finally:
         for v in NODES:
             c.dev[v].close()
@@ -45,3 +51,11 @@ def test_limited(monkeypatch):
 
 def test_moving(monkeypatch):
     _run("moving", monkeypatch)
+
+
+def test_compacting(monkeypatch):
+    _run("compacting", monkeypatch)
+
+
+def test_compacting_moving(monkeypatch):
+    _run("compacting_moving", monkeypatch)
