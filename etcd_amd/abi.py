@@ -145,6 +145,7 @@ HB_PHASE_FINISH = 3
 HB_PHASE_COUNT = 4
 HB_KERN_ROUTE_FAST = 1  # hb_step_kernels: k_route_fast ran the route and the fast lane
 HB_KERN_ROUTE_ELECT = 2  # hb_step_kernels: k_route closed storm partitions and ran the election lane
+HB_KERN_ROUTE_FAST_WIDE = 4  # hb_step_kernels: k_route_fast ran in its wide form (1,024 lanes)
 
 STAT_NAMES = ["msgs", "appresp", "voteresp", "dropped", "commits", "won", "lost",
               "events", "faults", "entries"]

@@ -1870,18 +1870,22 @@ __global__ void __launch_bounds__(PART, HB_FAST_WAVES) k_apply_fast(ApplyArgs a)
 }
 
 // ---------------------------------------------------------------------------
-// k_route_fast<KMAX, X>: k_route<KMAX, X> and k_apply_fast<3, X, KMAX> in one
+// k_route_fast<KMAX, X, WIDE>: k_route<KMAX, X> and k_apply_fast<3, X, KMAX> in one
 // workgroup (n = 3, prep and apply on one stream).  The route phase stages
 // each of the workgroup's RG groups' first KMAX messages (and, X mode, their
 // extensions) in LDS exactly as k_route does; the fast lane then reads them
 // from there instead of from the slot arrays, so the slots are neither
 // written nor read back (16 + 16 B per message in X mode, plus the count, each
 // way).  Only a group the fast lane hands over gets its count and slots
-// written to HBM, where k_apply reads them.  512 lanes per workgroup and at
-// most ~73 KB of LDS (RG = 2048 groups for two leader-side slots, fewer when
-// a group keeps more bytes): two workgroups per CU, each lane stepping
-// RG / 512 groups in turn, with no barrier between them (the partitions'
-// event cursors and hand-over masks stay in LDS until the end).  Measured on
+// written to HBM, where k_apply reads them.  Narrow form: 512 lanes per
+// workgroup and at most ~73 KB of LDS (RG = 2048 groups for two leader-side
+// slots, fewer when a group keeps more bytes), two workgroups per CU; wide
+// form (RouteFastGeom, below): twice the lanes, groups and LDS, one workgroup
+// per CU.  Each lane steps RG / lanes groups in turn, with no barrier between
+// them (the partitions' event cursors and hand-over masks stay in LDS until
+// the end).  A workgroup that owns its whole bucket (W = 1) places its
+// partitions' M event chunks by a prefix in LDS; sisters share the bucket's
+// cursor in bk_fill.  Measured on
 // cfg2 (same-box A/Bs) and not kept: 1024-group workgroups of 256 or 512
 // lanes (+6-9 %), 8 or 16 records in flight per lane in the route phase
 // (0 / +1.5 %), the slots staged as four 4-byte planes (neutral), the group
@@ -1894,20 +1898,24 @@ __global__ void __launch_bounds__(PART, HB_FAST_WAVES) k_apply_fast(ApplyArgs a)
 #ifndef HB_RF_UNROLL
 #define HB_RF_UNROLL 4  // records in flight per lane in the route phase
 #endif
-#ifndef HB_RF_THREADS
-#define HB_RF_THREADS 512
-#endif
-#ifndef HB_RF_RG_LOG
-#define HB_RF_RG_LOG 11  // (two leader-side slots; each doubling of a group's LDS bytes halves it)
-#endif
 #ifndef HB_RF_WAVES
 #define HB_RF_WAVES 4
 #endif
-constexpr uint32_t RF_THREADS = HB_RF_THREADS;
 constexpr uint32_t RF_UNROLL = HB_RF_UNROLL;
-template <uint32_t KMAX, bool X> struct RouteFastGeom {
-  // 16 B per slot, twice in X mode: 2 slots x 2048, 3 x 1024, X 2 x 1024, X 3 x 512 groups
-  static constexpr uint32_t RG_LOG = HB_RF_RG_LOG - (KMAX > 2 ? 1u : 0u) - (X ? 1u : 0u);
+// The forms an eligible handle runs wide, bit (KMAX == 3) * 2 + X: <2, false>
+// (the leader-side step, measured: DESIGN §3.3a).  The other three keep narrow
+// until their own workloads are measured wide.
+constexpr uint32_t RF_WIDE_FORMS = 3u;
+// Two geometries, both compiled; the handle picks one at hb_create (rf_wide).
+// Narrow: 512 lanes, two workgroups per CU.  Wide: 1024 lanes and twice the
+// groups, one workgroup per CU with the same 16 waves and up to 148 KB of LDS:
+// for handles whose buckets hold 4096 groups or more, where a narrow
+// workgroup shares its bucket with a sister that streams the same records.
+// A lane steps RG / THREADS groups in either form.
+template <uint32_t KMAX, bool X, bool WIDE> struct RouteFastGeom {
+  static constexpr uint32_t THREADS = WIDE ? 1024 : 512;
+  // 16 B per slot, twice in X mode: 2 slots x 2048, 3 x 1024, X 2 x 1024, X 3 x 512 groups (wide: twice that)
+  static constexpr uint32_t RG_LOG = (WIDE ? 12u : 11u) - (KMAX > 2 ? 1u : 0u) - (X ? 1u : 0u);
   static constexpr uint32_t RG = 1u << RG_LOG;  // groups per workgroup
   static constexpr uint32_t NP = RG / PART;     // partitions per workgroup
 };
@@ -1925,7 +1933,7 @@ struct RouteFastGroup {
   }
 };
 
-// Pass 1 of k_route_fast<2, false> over a lane's RG / RF_THREADS groups: the
+// Pass 1 of k_route_fast<2, false> over a lane's RG / THREADS groups: the
 // group-waves whose lanes are all steady or idle are stepped here (what
 // fast_step's steady branch does, on SteadyIn instead of a FastLane), with the
 // next group's first round trip (SteadyHead) in flight under the current
@@ -1934,19 +1942,19 @@ struct RouteFastGroup {
 // (nothing is written before the vote) and its bit is set in the returned
 // mask; the wave owns its group-waves, so the mask is wave-uniform.  The
 // statistics a steady step can make non-zero are added to acc.
-template <uint32_t RG>
+template <uint32_t RG, uint32_t THREADS>
 __device__ __forceinline__ uint32_t steady_pass(const ApplyArgs& a, SteadyHead H, uint32_t part0,
                                                 const uint32_t* l_cnt, const uint4 (*l_slot)[RG],
                                                 const uint64_t* l_moff, uint32_t* l_pfill, uint32_t* l_fill,
                                                 uint32_t (&acc)[ST_N + 1], uint32_t& nsteady) {
-  constexpr uint32_t NW = RG / RF_THREADS;
+  constexpr uint32_t NW = RG / THREADS;
   uint32_t pend = 0;
   uint32_t msgs = 0, commits = 0, entries = 0, nev = 0;
   // (unrolled: the `k + 1 < NW` below must fold, or the loads under it sit
   // behind a join like the one SteadyHead::load avoids)
 #pragma unroll
   for (uint32_t k = 0; k < NW; ++k) {
-    const uint32_t i = threadIdx.x + k * RF_THREADS;
+    const uint32_t i = threadIdx.x + k * THREADS;
     const RouteFastGroup R(a, part0, i);
     SteadyIn L(a.S, R.g, H);
     const uint32_t prop_k = H.props;  // (0 unless the group is valid)
@@ -1967,7 +1975,7 @@ __device__ __forceinline__ uint32_t steady_pass(const ApplyArgs& a, SteadyHead H
            (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(moff >> 32)) << 32;
     // ---- the look-ahead: the next group's first round trip leaves now
     if (k + 1 < NW) {  // (uniform)
-      const RouteFastGroup N(a, part0, i + RF_THREADS);
+      const RouteFastGroup N(a, part0, i + THREADS);
       H.load(a.S, a.props, N.g, N.valid);
     }
     // ---- fast_step's steady branch
@@ -1999,11 +2007,11 @@ __device__ __forceinline__ uint32_t steady_pass(const ApplyArgs& a, SteadyHead H
   return (uint32_t)__builtin_amdgcn_readfirstlane(pend);
 }
 
-template <uint32_t KMAX, bool X>
-__global__ void __launch_bounds__(RF_THREADS, HB_RF_WAVES) k_route_fast(ApplyArgs a) {
+template <uint32_t KMAX, bool X, bool WIDE>
+__global__ void __launch_bounds__((RouteFastGeom<KMAX, X, WIDE>::THREADS), HB_RF_WAVES) k_route_fast(ApplyArgs a) {
   constexpr int NMAX = 3;
-  using GM = RouteFastGeom<KMAX, X>;
-  constexpr uint32_t RG = GM::RG, NP = GM::NP;
+  using GM = RouteFastGeom<KMAX, X, WIDE>;
+  constexpr uint32_t RG = GM::RG, NP = GM::NP, RF_THREADS = GM::THREADS;
   const uint32_t sl = a.sis_log, W = 1u << (PART_LOG + sl - GM::RG_LOG);
   __shared__ uint32_t l_cnt[RG];
   __shared__ uint4 l_slot[KMAX][RG];
@@ -2085,7 +2093,15 @@ __global__ void __launch_bounds__(RF_THREADS, HB_RF_WAVES) k_route_fast(ApplyArg
     const uint32_t part = part0 + tid;
     uint64_t mo = 0;
     if (part < a.NB) {
-      const uint32_t r = atomicAdd(&a.bk_fill[bk * CTR_STRIDE], a.ev_per_msg * (l_ptot[tid] + PART * a.props_on));
+      uint32_t r = 0;
+      if (W == 1) {  // (uniform) the bucket is this workgroup's: its partitions' chunks in order, no cursor
+        for (uint32_t j = 0; j < NP; ++j) {
+          const uint32_t n = a.ev_per_msg * (l_ptot[j] + PART * a.props_on);
+          r += j < tid ? n : 0u;  // (a partition past NB has no lower sister inside NB)
+        }
+      } else {
+        r = atomicAdd(&a.bk_fill[bk * CTR_STRIDE], a.ev_per_msg * (l_ptot[tid] + PART * a.props_on));
+      }
       mo = (uint64_t)a.ev_per_msg * ((uint64_t)a.NB * PART + lo + ((uint64_t)bk * PART << sl) * a.props_on) + r;
       a.ev_off[2 * part + 1] = mo;
     }
@@ -2105,7 +2121,7 @@ __global__ void __launch_bounds__(RF_THREADS, HB_RF_WAVES) k_route_fast(ApplyArg
   uint32_t pend = (1u << (RG / RF_THREADS)) - 1;
   if constexpr (STEADY) {
     if (a.steady)  // (uniform)
-      pend = steady_pass<RG>(a, H0, part0, l_cnt, l_slot, l_moff, l_pfill, l_fill, acc, nsteady);
+      pend = steady_pass<RG, RF_THREADS>(a, H0, part0, l_cnt, l_slot, l_moff, l_pfill, l_fill, acc, nsteady);
   }
   for (uint32_t i = tid, kw = 0; i < RG; i += RF_THREADS, ++kw) {
     if (STEADY && !((pend >> kw) & 1u)) continue;  // (uniform) stepped by pass 1
@@ -5709,6 +5725,7 @@ struct hb_handle {
   uint32_t next_set = 0, cur = 0;  // set of the next / the last step
   uint32_t NBK = 0;               // buckets
   uint32_t sis_log = SIS_LOG_MAX;  // partitions per bucket (log2)
+  uint32_t rf_wide = 0;            // the forms of k_route_fast this handle runs wide (route_fast_form bits)
   uint32_t passes = 1;
   // small steps (a few thousand messages, hb_step / hb_events_to_host): one
   // launch for the partition and one for the event words; HB_SMALL_STEP=0
@@ -5970,25 +5987,37 @@ T* dev_view(T* p) {
 }
 
 // The apply kernels; ev = this step's phase events (HB_STEP_PROFILE) or null.
-template <uint32_t KMAX, bool X>
+template <uint32_t KMAX, bool X, bool WIDE>
 void launch_route_fast_t(hb_handle* h, const ApplyArgs& a) {
-  hipLaunchKernelGGL((k_route_fast<KMAX, X>),
-                     dim3(((h->NBK + 7) & ~7u) << (PART_LOG + h->sis_log - RouteFastGeom<KMAX, X>::RG_LOG)),
-                     dim3(RF_THREADS), 0, h->stream, a);
+  using GM = RouteFastGeom<KMAX, X, WIDE>;
+  hipLaunchKernelGGL((k_route_fast<KMAX, X, WIDE>), dim3(((h->NBK + 7) & ~7u) << (PART_LOG + h->sis_log - GM::RG_LOG)),
+                     dim3(GM::THREADS), 0, h->stream, a);
 }
-void launch_route_fast(hb_handle* h, const ApplyArgs& a) {
+template <bool WIDE>
+void launch_route_fast_w(hb_handle* h, const ApplyArgs& a) {
   if (a.kmax == 3) {
-    if (a.slotx) launch_route_fast_t<3, true>(h, a);
-    else launch_route_fast_t<3, false>(h, a);
+    if (a.slotx) launch_route_fast_t<3, true, WIDE>(h, a);
+    else launch_route_fast_t<3, false, WIDE>(h, a);
   } else {
-    if (a.slotx) launch_route_fast_t<2, true>(h, a);
-    else launch_route_fast_t<2, false>(h, a);
+    if (a.slotx) launch_route_fast_t<2, true, WIDE>(h, a);
+    else launch_route_fast_t<2, false, WIDE>(h, a);
   }
 }
-// the largest route-fast workgroup (groups, log2) of a step
-inline uint32_t route_fast_rg_log(uint32_t kmax, bool x) {
-  return kmax == 3 ? (x ? RouteFastGeom<3, true>::RG_LOG : RouteFastGeom<3, false>::RG_LOG)
-                   : (x ? RouteFastGeom<2, true>::RG_LOG : RouteFastGeom<2, false>::RG_LOG);
+// One bit of hb_handle::rf_wide per form of k_route_fast.
+inline uint32_t route_fast_form(uint32_t kmax, bool x) { return 1u << ((kmax == 3 ? 2u : 0u) + (x ? 1u : 0u)); }
+inline bool route_fast_wide(const hb_handle* h, uint32_t kmax, bool x) { return h->rf_wide & route_fast_form(kmax, x); }
+void launch_route_fast(hb_handle* h, const ApplyArgs& a) {
+  if (route_fast_wide(h, a.kmax, a.slotx != nullptr)) launch_route_fast_w<true>(h, a);
+  else launch_route_fast_w<false>(h, a);
+}
+// the route-fast workgroup (groups, log2) of a step: the wide form's is one more
+template <bool WIDE>
+constexpr uint32_t route_fast_rg_log_w(uint32_t kmax, bool x) {
+  return kmax == 3 ? (x ? RouteFastGeom<3, true, WIDE>::RG_LOG : RouteFastGeom<3, false, WIDE>::RG_LOG)
+                   : (x ? RouteFastGeom<2, true, WIDE>::RG_LOG : RouteFastGeom<2, false, WIDE>::RG_LOG);
+}
+inline uint32_t route_fast_rg_log(const hb_handle* h, uint32_t kmax, bool x) {
+  return route_fast_wide(h, kmax, x) ? route_fast_rg_log_w<true>(kmax, x) : route_fast_rg_log_w<false>(kmax, x);
 }
 // fused: k_route_fast stood in for k_route + k_apply_fast (launched by hb_step)
 template <int NMAX>
@@ -6116,6 +6145,14 @@ int hb_create(int device, uint32_t capacity, uint32_t max_replicas, uint32_t max
   if (const char* e = getenv("HB_SIS_LOG")) {  // (A/B knob: a fixed bucket size, within the allowed range)
     const int v = atoi(e);
     if (v >= (int)sl_min && v <= (int)sl_max) h->sis_log = (uint32_t)v;
+  }
+  // k_route_fast's geometry: wide where a narrow <2, false> workgroup would
+  // have a sister (n = 3, buckets of 4096 groups or more), in the forms that
+  // measured no slower wide (RF_WIDE_FORMS); HB_RF_WIDE=1: every form, 0: none
+  // (A/B knob, within that range).
+  if (h->nmax == 3 && PART_LOG + h->sis_log >= RouteFastGeom<2, false, true>::RG_LOG) {
+    h->rf_wide = RF_WIDE_FORMS;
+    if (const char* e = getenv("HB_RF_WIDE")) h->rf_wide = atoi(e) ? 0xFu : 0u;
   }
   h->NBK = nbk_for(h->sis_log);
   h->passes = passes_for(h->sis_log);
@@ -7069,7 +7106,7 @@ int hb_step(hb_handle* h, const hb_batch* b, uint32_t flags) {
   // kernel's workgroups (k_route_fast; two-pass handles too: cfg5 0.998 ->
   // 0.931 ms/step same box)
   const bool fused = h->nmax == 3 && !two && (h->fuse >= 2 || (h->fuse == 1 && h->passes == 1)) &&
-                     PART_LOG + h->sis_log >= route_fast_rg_log(aa.kmax, xmode);
+                     PART_LOG + h->sis_log >= route_fast_rg_log(h, aa.kmax, xmode);
   // Egress: the term and last columns as they are before this step, on the
   // apply stream.  One stream: the route below is the first kernel that can
   // write them (its storm hand-over runs the election lane).  Two stages: the
@@ -7108,7 +7145,8 @@ int hb_step(hb_handle* h, const hb_batch* b, uint32_t flags) {
     h->prof_n++;
   }
   h->stepped = true;
-  h->kern = (fused ? HB_KERN_ROUTE_FAST : 0u) | (aa.storm ? HB_KERN_ROUTE_ELECT : 0u);
+  h->kern = (fused ? HB_KERN_ROUTE_FAST : 0u) | (aa.storm ? HB_KERN_ROUTE_ELECT : 0u) |
+            (fused && route_fast_wide(h, aa.kmax, xmode) ? HB_KERN_ROUTE_FAST_WIDE : 0u);
   return HB_OK;
 }
 

@@ -1104,9 +1104,14 @@ int  hb_phase_reset(hb_handle* h);
  * k_apply_fast / k_apply_lead separately.  HB_KERN_ROUTE_ELECT = (n >= 5,
  * batches without dense proposals) the route closed the partitions whose
  * groups k_apply_lead would only hand over and ran the election lane there
- * (k_route<8, false, n>; HB_STORM=0 at hb_create turns it off). */
+ * (k_route<8, false, n>; HB_STORM=0 at hb_create turns it off).
+ * HB_KERN_ROUTE_FAST_WIDE = (with HB_KERN_ROUTE_FAST) k_route_fast ran in its
+ * wide form, 1,024 lanes and twice the groups per workgroup: the choice of an
+ * n = 3 handle whose buckets hold 4,096 groups or more (HB_RF_WIDE=0 / 1 at
+ * hb_create overrides it there). */
 #define HB_KERN_ROUTE_FAST 1u
 #define HB_KERN_ROUTE_ELECT 2u
+#define HB_KERN_ROUTE_FAST_WIDE 4u
 int  hb_step_kernels(hb_handle* h, uint32_t* mask);
 /* The n = 3 fast lane steps a wave whose 64 groups are all in steady
  * replication (or have nothing to step) by a straight-line path; HB_FAST_STEADY=0
